@@ -5,7 +5,14 @@ One step = one pass of the hot path (parse -> LPM -> first-match scan ->
 per-rule stats) over one resident batch of synthetic SoA packets per GPU, plus
 (N > 1) the RCCL all-reduce of the 1024 x 4 u64 per-rule statistics.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds
+what takes runs of its own: the CPU baseline (the oracle on the host cores, checked
+against the device's result words) and the in-process line-rate probe that
+`random_line_model` prices the profile's line counts with.  --dump-outputs DIR
+writes what the last timed step computed (result words, per-rule counters) as
+DIR/<name>.npy, for comparing two builds output for output.
 
 Launch: with --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts
 N rank processes itself (torch.multiprocessing spawn; the parent never touches
@@ -151,7 +158,7 @@ def parse(argv=None):
     ap.add_argument("--key-order", choices=("shuffled", "workload"), default="shuffled",
                     help="order of the table updates: seeded random like the reference's Go map range (default), "
                          "or the generator's popularity order (same map either way)")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1 << 27, help="packets per GPU per step")
     ap.add_argument("--cfg", type=int, default=2, choices=[1, 2, 4])
@@ -162,12 +169,21 @@ def parse(argv=None):
                     help="sources uniform over the prefixes instead of the config's Zipf(1.1) (cache-hostile variant)")
     ap.add_argument("--global-packets", type=int, default=0,
                     help="fixed job of this many packets sharded over the ranks (strong scaling, configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (cpu_baseline) and the "
+                         "line-rate probe (line_rates, random_line_model); --no-cpu-baseline / --no-line-rates drop "
+                         "either again")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float64): results "
+                         "(the result words in packet order; a fixed seeded sample of a large batch) and stats (the "
+                         "step's 1024 x 4 per-rule counters).  With several ranks or --global-packets, results are "
+                         "rank 0's shard and stats the all-reduced block; --in-process writes results_slot<s> per slot")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="packets in the CPU-baseline sample (0: ~10-20 s of oracle work on the usable cores)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="oracle threads (0: every usable core)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-line-rates", action="store_true",
-                    help="skip the in-process random-line / stream rate probe (and so random_line_model)")
+                    help="with --full: skip the in-process random-line / stream rate probe (and so random_line_model)")
     ap.add_argument("--traffic-json", default=None,
                     help="PMC traffic summary (default profiles/traffic_<workload>.json when it matches the kernel)")
     ap.add_argument("--layout", default="standard", choices=["compact", "standard"],
@@ -204,6 +220,8 @@ def parse(argv=None):
                     help="with --from-frames: one kernel classifies straight from the frames (infw_classify_frames), "
                          "no SoA batch written or read; checked untimed against the packer path's results")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
     if args.xdp_ring:
         args.from_frames = args.from_frames or 2048
         args.fused = True
@@ -616,7 +634,7 @@ def run_rank(args):
     ex = StatsExchange(lambda: torch.zeros((1024, 4), dtype=torch.int64, device=dev), use_dist)
     # the device's random-line and stream rates, measured in this process just before the timed loop (same lease,
     # same device): what random_line_model prices the kernel's PMC line counts with (~0.3 s, untimed)
-    rates = None if args.no_line_rates else probe_line_rates(W, local, log)
+    rates = probe_line_rates(W, local, log) if args.full and not args.no_line_rates else None
     torch.cuda.synchronize()
     stream = torch.cuda.current_stream(dev)
 
@@ -911,12 +929,20 @@ def run_rank(args):
         "cpu_baseline": None,
     }
 
-    # ---- CPU baseline: the oracle (plain C restatement of kernel.c) on host cores, rank 0, N=1 only
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and n:
+    want_baseline = args.full and world == 1 and not args.no_cpu_baseline and n
+    if rank == 0 and (args.dump_outputs or want_baseline):
+        if args.xdp_ring in HOST_FED and n:  # the last step's words, where the library left them: the rings' host arrays
+            results = torch.cat(host_res).to(dev)
         if perm is not None:  # the rings' results back into packet order
             in_order = torch.empty_like(results)
             in_order[perm] = results
             results = in_order
+    if args.dump_outputs and rank == 0:
+        last = ex.bufs[(args.steps - 1) & 1]  # the last step's (all-reduced) counter block
+        dump_outputs(args.dump_outputs, {"results": sample_words(results), "stats": last.cpu().numpy()})
+
+    # ---- CPU baseline (--full): the oracle (plain C restatement of kernel.c) on host cores, rank 0, N=1 only
+    if want_baseline and rank == 0:
         out["cpu_baseline"] = cpu_baseline(args, wl, results, n, start)
 
     if rank == 0:
@@ -924,6 +950,29 @@ def run_rank(args):
     clf.stats_bind(0, None)
     if use_dist:
         dist.destroy_process_group()
+
+
+DUMP_WORDS = 1 << 22  # result words per dumped array: 32 MiB as float64
+
+
+def sample_words(results, k=DUMP_WORDS):
+    """A device tensor of u32 result words as a float64 array (exact): all of it, or — past k words — the words at k
+    fixed, seeded, ascending positions (the same for every run of the same batch size)."""
+    import numpy as np
+    import torch
+    n = results.numel()
+    if n > k:
+        idx = np.sort(np.random.default_rng(20240229).integers(0, n, size=k))
+        results = results[torch.from_numpy(idx).to(results.device)]
+    return results.cpu().numpy().view(np.uint32).astype(np.float64)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as DIRECTORY/<name>.npy in float64."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a).astype(np.float64))
 
 
 def probe_line_rates(W, ordinal, log):
@@ -1062,6 +1111,9 @@ def run_in_process(args, n_slots):
         "per_slot": [{"slot": s, "device": devices[s], "packets_per_step": shards[s][1],
                       "kernel_ms_avg": round(kern[s], 4)} for s in range(n_slots)],
     }
+    if args.dump_outputs:  # every slot's words and one step's counters summed over the slots (each step's are equal)
+        dump_outputs(args.dump_outputs, {**{f"results_slot{s}": sample_words(results[s], DUMP_WORDS // n_slots)
+                                            for s in range(n_slots)}, "stats": digest_block})
     print(json.dumps(out), flush=True)
     clf.close()
 

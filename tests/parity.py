@@ -21,6 +21,54 @@ def oracle_for(wl: W.Workload) -> "orc.OracleMap":
     return m
 
 
+_REGISTER_REFUSED = []
+
+
+def host_register_refused():
+    """None where the HIP runtime page-locks memory the process already owns, else the runtime's own refusal as text.
+    Asked of the runtime itself (hipHostRegister of one anonymous page through ctypes, on the libamdhip64 this process
+    already runs), not of the library under test: where the runtime accepts the page, a failing infw_host_register
+    fails its tests.  Some virtualised GPU hosts refuse every registration of a user mapping (shared or private,
+    touched or not, any flag: hipErrorInvalidValue) although RLIMIT_MEMLOCK is unlimited, mlock() of the same page
+    succeeds and hipHostMalloc works: the refusal is the platform's (no user-pointer mappings for the device there),
+    not a locked-memory limit.  The probe's sticky error is consumed; asked once per process."""
+    if not _REGISTER_REFUSED:
+        import ctypes as C
+        import mmap
+        path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64.so" in ln)
+        hip = C.CDLL(path)
+        hip.hipHostRegister.argtypes = [C.c_void_p, C.c_size_t, C.c_uint]
+        hip.hipHostUnregister.argtypes = [C.c_void_p]
+        hip.hipGetErrorString.restype = C.c_char_p
+        mm = mmap.mmap(-1, 4096)
+        buf = C.c_char.from_buffer(mm)
+        e = hip.hipHostRegister(C.addressof(buf), 4096, 0)
+        if e == 0:
+            assert hip.hipHostUnregister(C.addressof(buf)) == 0
+            _REGISTER_REFUSED.append(None)
+        else:
+            hip.hipGetLastError()
+            _REGISTER_REFUSED.append(f"hipHostRegister of one anonymous page: {hip.hipGetErrorString(e).decode()}")
+        del buf
+    return _REGISTER_REFUSED[0]
+
+
+def need_host_register():
+    """Skips the calling test, before it does any work, where the HIP runtime itself refuses to page-lock memory the
+    process already owns (host_register_refused): infw_host_register cannot work there."""
+    import pytest
+    why = host_register_refused()
+    if why:
+        pytest.skip(f"needs hipHostRegister of the process's own memory, which the HIP runtime here refuses ({why})")
+
+
+def pinned(a: np.ndarray) -> np.ndarray:
+    """A copy of `a` in page-locked host memory allocated as such (hipHostMalloc, through torch); the array keeps its
+    tensor alive."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().numpy()
+
+
 def oracle_run(m, wl: W.Workload, start: int, n: int, threads: int = 8):
     hdr, cap, pl, ifx = wl.frames(start, n)
     res, ver, stats, _ = m.classify_frames(hdr, cap, pl, ifx, nthreads=threads)

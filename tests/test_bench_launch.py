@@ -109,3 +109,22 @@ def test_host_counters_match_stats_from_results():
     res = (rng.integers(0, 1200, 5000).astype(np.uint32) << 8) | rng.integers(0, 4, 5000).astype(np.uint32)
     pl = rng.integers(60, 9000, 5000).astype(np.uint32)
     assert np.array_equal(host_counters(res, pl), stats_from_results(res, pl))
+
+
+def test_dump_sample_is_fixed_and_exact(tmp_path):
+    """--dump-outputs' sample of a large result array: the same ascending positions on every call, the words exact in
+    float64 (u32 words with the top bit set included); a small array is dumped whole."""
+    import torch
+
+    import bench
+    words = (np.arange(100000, dtype=np.uint64) * 2654435761 % (1 << 32)).astype(np.uint32)
+    t = torch.from_numpy(words.view(np.int32))
+    a, b = bench.sample_words(t, 1000), bench.sample_words(t, 1000)
+    assert a.dtype == np.float64 and a.shape == (1000,) and np.array_equal(a, b)
+    order = np.argsort(words)  # the words are distinct (an odd multiplier mod 2^32): each sample names its position
+    at = order[np.searchsorted(words[order], a.astype(np.uint32))]
+    assert np.array_equal(words[at].astype(np.float64), a) and np.all(np.diff(at) >= 0) and (a >= 2.0 ** 31).any()
+    assert np.array_equal(bench.sample_words(t, 100000), words.astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "d"), {"x": words, "y": np.ones((2, 3), np.int64)})
+    x, y = np.load(tmp_path / "d" / "x.npy"), np.load(tmp_path / "d" / "y.npy")
+    assert x.dtype == y.dtype == np.float64 and np.array_equal(x, words) and y.shape == (2, 3)

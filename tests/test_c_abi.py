@@ -55,6 +55,8 @@ def test_c_xdp_caller_host_only(tmp_path):
 def test_c_xdp_caller_on_device(tmp_path):
     """A daemon's own (registered) umem, ring and result arrays through infw_classify_xdp, two interface rings; the
     same memory unregistered refused by it (-EFAULT) and classified by the host-fed path (infw_classify_xdp_host)."""
+    from parity import need_host_register
+    need_host_register()
     exe = build_xdp_demo(tmp_path)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr

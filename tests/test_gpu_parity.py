@@ -16,7 +16,8 @@ import infw  # noqa: E402
 from infw import workloads as W  # noqa: E402
 from infw.batch import SoaBatch  # noqa: E402
 
-from parity import assert_parity, check_cfg, gpu_run, oracle_for, stats_from_results  # noqa: E402
+from parity import (assert_parity, check_cfg, gpu_run, host_register_refused, oracle_for, pinned,  # noqa: E402
+                    stats_from_results)
 
 _SHORT = {"dir24": 0, "compressed": 1}  # option short_table (include/infw.h)
 
@@ -1091,7 +1092,14 @@ def test_lds_d16_cache_collisions(monkeypatch):
 def test_classify_host_batches(monkeypatch, split):
     """infw_classify_host: a host-resident batch pipelined through the device in chunks (ragged last chunk,
     pageable and page-locked memory) gives the same result words, verdicts and counters as the oracle — also in
-    the two-phase form, whose per-chunk scratch is allocated on the pipeline's kernel stream."""
+    the two-phase form, whose per-chunk scratch is allocated on the pipeline's kernel stream.
+
+    Page-locked memory comes two ways.  Registered in place with infw_host_register (the daemon's case), wherever the
+    HIP runtime itself registers a page of the process's own memory (parity.host_register_refused, asked of the
+    runtime, not of the library: a failing infw_host_register fails this test there).  And allocated pinned, on every
+    machine: infw_classify_host hands the caller's pointers to hipMemcpyAsync and nothing else (abi.cpp
+    classify_host_chunks: no pointer query, no branch on the memory's kind), so the library's path is the same for
+    both and only the runtime's copy engine sees the difference."""
     if split:
         monkeypatch.setitem(infw.DEFAULT_OPTIONS, "split", int(split))
     wl = W.Workload(W.CFG2_MIXED_1M, n_prefixes=50000, n_templates=256)
@@ -1103,18 +1111,22 @@ def test_classify_host_batches(monkeypatch, split):
     hdr, cap, pl, ifx = wl.frames(0, n)
     ores, over, ost, _ = m.classify_frames(hdr, cap, pl, ifx, nthreads=8)
     soa = infw.HostSoa.from_tuples(wl.tuples(0, n))
-    for chunk, pin in ((65536, False), (1 << 22, True)):
-        if pin:
+    legs = [(65536, "pageable")] + ([(1 << 22, "registered")] if host_register_refused() is None else []) + [
+        (1 << 22, "pinned")]
+    for chunk, memory in legs:
+        if memory == "registered":
             for a in soa.arrays():
                 clf.host_register(a)
+        elif memory == "pinned":  # the same streams in memory allocated page-locked
+            soa.saddr, soa.ifindex, soa.pkt_len, soa.meta, soa.l4word = (pinned(a) for a in soa.arrays())
         res = np.zeros(n, np.uint32)
         ver = np.zeros(n, np.uint8)
         clf.stats_reset()
         clf.classify_host(soa, res, ver, chunk=chunk)
-        assert np.array_equal(res, ores), chunk
-        assert np.array_equal(ver, over), chunk
-        assert np.array_equal(clf.stats_read_all(), ost), chunk
-        if pin:
+        assert np.array_equal(res, ores), (chunk, memory)
+        assert np.array_equal(ver, over), (chunk, memory)
+        assert np.array_equal(clf.stats_read_all(), ost), (chunk, memory)
+        if memory == "registered":
             for a in soa.arrays():
                 clf.host_unregister(a)
 

@@ -15,7 +15,7 @@ import torch
 import infw
 from infw import workloads as W
 
-from parity import oracle_for
+from parity import need_host_register, oracle_for
 from test_hostpack_cpu import ring
 
 pytestmark = pytest.mark.gpu
@@ -131,18 +131,67 @@ def test_xdp_host_equals_device_read(setup):
     assert np.array_equal(clf.stats_read_all(), gst)
 
 
-def test_xdp_device_read_rejects_pageable(setup):
-    """infw_classify_xdp on pageable memory (a socket's mmapped ring as it is) returns -EFAULT instead of faulting
-    the GPU; registered with infw_host_register, the same memory classifies."""
-    wl, clf, _ = setup
-    r = rings_of(wl, 123, [300], "aligned", seed=13)[0]
+def _own_mappings(r):
+    """The ring's umem and descriptors in the process's own anonymous mappings (page-aligned), as a daemon's."""
     maps, arrs = [], []
-    for a in (r["umem"], r["desc"]):  # the process's own anonymous mappings (page-aligned), as a daemon's
+    for a in (r["umem"], r["desc"]):
         mm = mmap.mmap(-1, max(a.nbytes, 4096))
         b = np.frombuffer(mm, dtype=a.dtype, count=a.size).reshape(a.shape)
         b[...] = a
         maps.append(mm)
         arrs.append(b)
+    return maps, arrs
+
+
+def test_xdp_device_read_of_pageable_is_efault(setup):
+    """infw_classify_xdp on pageable memory (a socket's mmapped ring as it is) returns -EFAULT instead of faulting the
+    GPU, whether or not the machine can register such memory; the host-fed path classifies the same memory."""
+    wl, clf, m = setup
+    r = rings_of(wl, 123, [300], "aligned", seed=13)[0]
+    maps, arrs = _own_mappings(r)
+    u, d = torch.from_numpy(arrs[0]), torch.from_numpy(arrs[1].view(np.int32))  # pageable CPU tensors
+    out = torch.empty(300, dtype=torch.int32, device="cuda:0")
+    for umem, desc in ((u, d), (u.pin_memory(), d), (u, d.pin_memory())):  # either argument pageable is refused
+        with pytest.raises(infw.InfwError) as e:
+            clf.classify_xdp(umem, desc, 300, r["ifindex"], results=out)
+        assert e.value.errno == 14
+    want, _, _ = oracle_of(m, [r])
+    got, _, _ = run_host(clf, [dict(r, umem=arrs[0], desc=arrs[1])], 0)
+    assert np.array_equal(got[0], want[0])
+    del u, d, arrs
+
+
+def test_refused_registration_leaves_no_error_behind(setup):
+    """A registration the runtime refuses (here: of a page that is registered already, or of any page where the
+    runtime registers none) returns -EIO and leaves no HIP error for the next launch to report."""
+    wl, clf, m = setup
+    mm = mmap.mmap(-1, 4096)
+    page = np.frombuffer(mm, dtype=np.uint8)
+    registered = False
+    try:
+        with pytest.raises(infw.InfwError) as e:
+            clf.host_register(page)
+            registered = True
+            clf.host_register(page)
+        assert e.value.errno == 5
+        rings = rings_of(wl, 4000, [700], "aligned", seed=3)
+        want, _, _ = oracle_of(m, rings)
+        got, _, _ = run_host(clf, rings, 0)
+        assert np.array_equal(got[0], want[0])
+    finally:
+        if registered:
+            clf.host_unregister(page)
+        del page
+
+
+def test_xdp_device_read_rejects_pageable(setup):
+    """infw_classify_xdp on pageable memory (a socket's mmapped ring as it is) returns -EFAULT instead of faulting
+    the GPU; registered with infw_host_register, the same memory classifies.  (The refusal alone, which needs no
+    registration, is test_xdp_device_read_of_pageable_is_efault.)"""
+    need_host_register()
+    wl, clf, _ = setup
+    r = rings_of(wl, 123, [300], "aligned", seed=13)[0]
+    maps, arrs = _own_mappings(r)
     u, d = torch.from_numpy(arrs[0]), torch.from_numpy(arrs[1].view(np.int32))  # pageable CPU tensors
     out = torch.empty(300, dtype=torch.int32, device="cuda:0")
     with pytest.raises(infw.InfwError) as e:

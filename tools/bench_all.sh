@@ -8,7 +8,7 @@ mkdir -p $OUT
 run() {  # name, args...
   local name=$1; shift
   if [ "$ONLY" != "  " ] && [[ "$ONLY" != *" $name "* ]]; then return 0; fi
-  timeout -k 10 300 python bench.py "$@" > $OUT/$name.log 2>&1
+  timeout -k 10 300 python bench.py --full "$@" > $OUT/$name.log 2>&1
   local rc=$?
   echo "$name rc=$rc"
   if [ $rc -ne 0 ]; then exit $rc; fi

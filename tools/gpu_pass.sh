@@ -65,7 +65,7 @@ step() {
       timeout -k 10 600 python -u tools/xdp_host_sweep.py --trace $sa >> $O/xdp_host_sweep.jsonl 2>> $O/xdp_host_sweep.trace || rc=$?
       tail -30 $O/xdp_host_sweep.jsonl ;;
     bench)
-      timeout -k 10 300 python -u bench.py > $O/bench_default.log 2>&1 || rc=$?
+      timeout -k 10 300 python -u bench.py --full > $O/bench_default.log 2>&1 || rc=$?
       tail -1 $O/bench_default.log | cut -c1-400 ;;
     lines)
       bash tools/bench_all.sh $O/lines || rc=$? ;;
@@ -73,12 +73,12 @@ step() {
       bash tools/bench_all.sh $O/lines $(echo ${s#lines:} | tr , ' ') || rc=$? ;;
     line:*)
       local a; a=$(args_of ${s#line:}) || return 2
-      timeout -k 10 300 python -u bench.py $a --no-cpu-baseline > $O/line_${s#line:}.log 2>&1 || rc=$?
+      timeout -k 10 300 python -u bench.py --full $a --no-cpu-baseline > $O/line_${s#line:}.log 2>&1 || rc=$?
       tail -1 $O/line_${s#line:}.log | cut -c1-300 ;;
     prof:*)
       local a; a=$(args_of ${s#prof:}) || return 2
       [ "${s#prof:}" = cfg3 ] && a="--global-packets 1073741824"
-      bash tools/profile.sh ${TAG}_${s#prof:} $a --steps 5 --warmup 1 --no-cpu-baseline || rc=$? ;;
+      bash tools/profile.sh ${TAG}_${s#prof:} $a --steps 5 --warmup 1 --full --no-cpu-baseline || rc=$? ;;
     lat:*)       # latency attribution PMC passes of one workload (tools/profile_lat.sh) into gpurun_out/lat_<tag>_<key>
       local a; a=$(args_of ${s#lat:}) || return 2
       bash tools/profile_lat.sh ${TAG}_${s#lat:} $a || rc=$? ;;

@@ -12,7 +12,7 @@ for r in $(seq 1 $R); do
   for f in $FEEDS; do
     IFS=: read -r ring order bs <<< "$f"
     tag=${ring}_${order}${bs:+_b$bs}_$r
-    timeout -k 10 300 python bench.py --xdp-ring $ring --umem-order $order ${bs:+--burst-size $bs} --no-cpu-baseline \
+    timeout -k 10 300 python bench.py --full --xdp-ring $ring --umem-order $order ${bs:+--burst-size $bs} --no-cpu-baseline \
         --steps 20 --warmup 3 > $OUT/$tag.log 2>&1 || exit $?
     python3 -c "import json; d=json.loads([l for l in open('$OUT/$tag.log') if l.startswith('{')][-1]); h=d['roofline']['xdp_ring']['host_feed']; print('$tag', d['value'], h['step_ms_min'], h['step_ms_median'], h['step_ms_max'], h['host_loadavg_1m'])"
   done

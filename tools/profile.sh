@@ -5,7 +5,7 @@
 # Stops at the first run that crashes / times out (rc >= 124).
 set -u
 TAG=${1:-r01}; shift || true
-ARGS=${*:-"--steps 5 --warmup 1 --no-cpu-baseline"}
+ARGS=${*:-"--steps 5 --warmup 1 --full --no-cpu-baseline"}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
