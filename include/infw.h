@@ -372,9 +372,35 @@ struct infw_xdp_desc {
 /* umem and descs are checked with hipPointerGetAttributes: -EFAULT when either */
 /* is ordinary (pageable, unregistered) host memory, which the GPU cannot read  */
 /* — register such a mapping with infw_host_register first, or use            */
-/* infw_classify_xdp_host, which reads it on the CPU.                          */
+/* infw_classify_xdp_host, which reads it on the CPU.  options is ignored: a    */
+/* socket bound with XDP_USE_SG feeds infw_classify_xdp_mb instead.            */
 int infw_classify_xdp(infw_ctx *ctx, int dev, const uint8_t *umem, const struct infw_xdp_desc *descs, uint64_t n,
                       uint32_t ifindex, uint32_t *result_words, uint8_t *xdp_verdicts, void *stream);
+
+/* A multi-buffer ring (socket bound with XDP_USE_SG; the reference program is */
+/* SEC("xdp.frags"), kernel.c:459): one frame per descriptor chain.            */
+/*   - descriptor i is a HEAD iff i == 0 or descriptor i-1 has PKT_CONTD clear; */
+/*   - a frame is a head plus the descriptors after it, up to and including    */
+/*     the first with PKT_CONTD clear; a chain still open at n-1 ends there    */
+/*     with what it has — pass whole frames;                                   */
+/*   - the frame is classified on the head's bytes only: linear length = the   */
+/*     head's len, frame length (bpf_xdp_get_buff_len(), the counters' bytes,  */
+/*     kernel.c:446, :450) = the sum of the chain's len, modulo 2^32;          */
+/*   - it is counted once in the per-rule counters;                            */
+/*   - a continuation descriptor's addr is never dereferenced;                 */
+/*   - every descriptor of the chain receives the head's result word and       */
+/*     verdict (result_words[i] / xdp_verdicts[i] stay per descriptor, so each */
+/*     buffer can be released or forwarded);                                   */
+/*   - other options bits are ignored.                                         */
+/* With every options == 0 it computes what infw_classify_xdp computes.        */
+/* Memory checks, alignment and errnos as infw_classify_xdp; -EINVAL for       */
+/* n >= 2^31, -ENOMEM when the per-call scratch (29 B per descriptor, stream-  */
+/* ordered from the context's pool) cannot be had.  Asynchronous on `stream`.  */
+/* No deny-event stream.  The host-fed calls below are single-buffer (they     */
+/* ignore options, as infw_classify_xdp does).                                 */
+#define INFW_XDP_PKT_CONTD (1u << 0)   /* linux/if_xdp.h XDP_PKT_CONTD */
+int infw_classify_xdp_mb(infw_ctx *ctx, int dev, const uint8_t *umem, const struct infw_xdp_desc *descs, uint64_t n,
+                         uint32_t ifindex, uint32_t *result_words, uint8_t *xdp_verdicts, void *stream);
 
 /* AF_XDP RX rings over a HOST umem, read by the CPU (the host-fed path): the */
 /* context's packer threads (option host_threads) read each frame's header    */

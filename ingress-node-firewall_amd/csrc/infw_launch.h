@@ -51,4 +51,13 @@ int infw_launch_variant_count(void);
 const char *infw_launch_variant_name(int i);
 // The launch shapes infw_set_launch accepts.
 int infw_launch_shape_ok(int block, int group, int blocks_per_cu);
+// infw_classify_xdp_mb (xdpchain.hip): a->umem / xdp / xdp_ifindex / n as for INFW_INPUT_XDP; the ring is compacted to
+// one frame per descriptor chain in scratch from a->pool, classified by infw_launch_classify as INFW_INPUT_FRAMES
+// (a->input is ignored) and the answers scattered to a->results / a->verdicts per descriptor.  Asynchronous.
+// 0, -EIO on a launch error, -ENOMEM when there is no pool or the scratch cannot be allocated.
+int infw_launch_classify_xdp_mb(const infw_launch_args *a);
 }
+// The chain pass's tiling: descriptors per workgroup of the reduce / emit kernels, tile summaries per round of the
+// carry kernel (infw/_native.py mirrors them for the tests' ring shapes).
+#define INFW_XDP_CHAIN_TILE 256
+#define INFW_XDP_CHAIN_CARRY 512

@@ -1,0 +1,245 @@
+// xdpchain.hip — a multi-buffer AF_XDP ring (XDP_USE_SG) -> one frame per descriptor chain (infw_classify_xdp_mb).
+//
+// The ring is compacted to an infw_frame_batch in scratch, the registered frames kernel classifies it once per frame
+// (infw_launch_classify, INFW_INPUT_FRAMES: selector, shapes and sidebands unchanged), and the answers are scattered
+// back to every descriptor of each chain.  Whether a descriptor heads a frame depends on its predecessor, a frame's
+// length is a sum over a run of descriptors that may cross waves, workgroups and tiles, and every descriptor needs its
+// frame's index: a segmented scan over the ring, done as three forward-only kernels so that no workgroup ever waits on
+// another (no look-back flags, no tickets):
+//
+//   xdp_chain_reduce   one workgroup per tile of kTile descriptors, one descriptor per lane -> the tile's summary
+//                      {heads in the tile, sum of len from its last head to its end (the whole tile if it has none)}
+//   xdp_chain_carry    one workgroup: exclusive scan of the summaries with (h1,l1) o (h2,l2) = (h1+h2, h2 ? l2 : l1+l2),
+//                      in place, kCarry summaries per round -> per tile {frames before it, length a chain open
+//                      at its start already has}, and the ring's frame count
+//   xdp_chain_emit     per tile again, with its carry: frame_of[i]; a head writes its frame's umem offset and linear
+//                      length, the chain's closing descriptor the frame length; slots past the frame count are zeroed
+//                      (linear length 0: the frames kernel reads nothing for them and counts nothing)
+//   xdp_chain_scatter  result_words[i] = frame results[frame_of[i]], verdicts alike
+//
+// Within a wave the head mask is one ballot; a lane's distance to its chain's head follows from the mask by clz, and
+// the segmented sum is a DPP scan (row_shr 1/2/4/8, row_bcast 15/31) whose every step is guarded by that distance.
+// The waves of a tile are combined through LDS.  A continuation's addr is never used.
+#include <hip/hip_runtime.h>
+#include <errno.h>
+#include <stdint.h>
+
+#include "../../include/infw.h"
+#include "infw_launch.h"
+
+namespace {
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTile = INFW_XDP_CHAIN_TILE;    // descriptors per workgroup = threads: one descriptor per lane
+constexpr int kWaves = kTile / 64;
+constexpr int kCarry = INFW_XDP_CHAIN_CARRY;  // summaries per round of the carry kernel = its threads
+static_assert(kTile % 64 == 0 && kCarry % 64 == 0 && kTile <= 1024 && kCarry <= 1024, "whole waves, one workgroup");
+
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ uint32_t dpp0(uint32_t v) {  // lanes without a source (or masked off) read 0
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, kRowMask, 0xF, false);
+}
+constexpr int kRowShr = 0x110, kWaveShr1 = 0x138, kRowBcast15 = 0x142, kRowBcast31 = 0x143;
+
+struct LaneScan {
+    uint32_t len;     // the descriptor's len (0 past the ring)
+    uint32_t opt;     // its options
+    uint64_t addr;
+    bool head;        // first descriptor of a frame
+    uint32_t heads;   // heads of the wave at or below this lane
+    uint32_t wheads;  // heads of the whole wave
+    uint32_t sum;     // len summed from the lane's head — or from the wave's lane 0 when heads == 0 — to the lane
+};
+
+// One descriptor per lane, every lane of the wave active.  Descriptor i heads a frame iff i == 0 or descriptor i - 1
+// has PKT_CONTD clear: the predecessor's options come from the lane below (DPP wave_shr), the wave's lane 0 reads them.
+__device__ __forceinline__ LaneScan scan_wave(const infw_xdp_desc *__restrict__ descs, uint64_t i, uint64_t n) {
+    const uint32_t lane = threadIdx.x & 63u;
+    LaneScan s{};
+    if (i < n) {
+        const u32x4 d = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(descs) + i);
+        s.addr = (uint64_t)d[1] << 32 | d[0];
+        s.len = d[2];
+        s.opt = d[3];
+    }
+    uint32_t prev = dpp0<kWaveShr1, 0xF>(s.opt);
+    if (lane == 0 && i > 0 && i < n) prev = __builtin_nontemporal_load(&descs[i - 1].options);
+    s.head = i < n && (i == 0 || !(prev & INFW_XDP_PKT_CONTD));
+    const uint64_t m = __ballot(s.head);
+    const uint64_t below = m & (~0ull >> (63u - lane));
+    s.heads = (uint32_t)__popcll(below);
+    s.wheads = (uint32_t)__popcll(m);
+    // lanes below this one that belong to the same run (all of them when the wave has no head at or below it)
+    const uint32_t dist = below ? lane - (63u - (uint32_t)__clzll(below)) : lane;
+    uint32_t x = s.len, t;
+    // within a row of 16: after the step of d, x covers [max(head, row start, lane - 2d + 1), lane]
+    t = dpp0<kRowShr + 1, 0xF>(x);
+    if (dist >= 1) x += t;
+    t = dpp0<kRowShr + 2, 0xF>(x);
+    if (dist >= 2) x += t;
+    t = dpp0<kRowShr + 4, 0xF>(x);
+    if (dist >= 4) x += t;
+    t = dpp0<kRowShr + 8, 0xF>(x);
+    if (dist >= 8) x += t;
+    // rows 1 and 3 take the row below's last lane when the run started before their row, then lanes 32..63 take
+    // lane 31 (by then complete from lane 0) when it started before lane 32
+    t = dpp0<kRowBcast15, 0xA>(x);
+    if ((lane & 16u) && dist > (lane & 15u)) x += t;
+    t = dpp0<kRowBcast31, 0xC>(x);
+    if ((lane & 32u) && dist > (lane & 31u)) x += t;
+    s.sum = x;
+    return s;
+}
+
+// (h1, l1) o (h2, l2) = (h1 + h2, h2 ? l2 : l1 + l2): runs of descriptors appended left to right
+__device__ __forceinline__ uint2 chain_op(uint2 a, uint2 b) { return make_uint2(a.x + b.x, b.x ? b.y : a.y + b.y); }
+
+__global__ __launch_bounds__(kTile) void xdp_chain_reduce(const infw_xdp_desc *__restrict__ descs, uint64_t n,
+                                                           uint2 *__restrict__ tiles) {
+    __shared__ uint2 s_w[kWaves];
+    const LaneScan s = scan_wave(descs, (uint64_t)blockIdx.x * kTile + threadIdx.x, n);
+    if ((threadIdx.x & 63u) == 63u) s_w[threadIdx.x >> 6] = make_uint2(s.wheads, s.sum);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint2 t = s_w[0];
+        for (int w = 1; w < kWaves; w++) t = chain_op(t, s_w[w]);
+        tiles[blockIdx.x] = t;
+    }
+}
+
+// Exclusive scan of the tile summaries, in place (a thread reads its own summary before it writes its carry), and the
+// ring's frame count.  One workgroup; kCarry summaries per round, the rounds chained by the running total.
+__global__ __launch_bounds__(kCarry) void xdp_chain_carry(uint2 *__restrict__ tiles, uint32_t n_tiles,
+                                                           uint32_t *__restrict__ n_frames) {
+    __shared__ uint2 s_w[kCarry / 64];
+    __shared__ uint2 s_total;
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    uint2 run = make_uint2(0u, 0u);
+    // the rounds are one serial chain, so a round's summaries are loaded a round ahead: their latency overlaps the
+    // scan and the barriers of the round before (nobody has written them yet: a thread writes only its own slot)
+    uint2 next = threadIdx.x < n_tiles ? tiles[threadIdx.x] : make_uint2(0u, 0u);
+    for (uint32_t base = 0; base < n_tiles; base += kCarry) {  // block-uniform trip count (the barriers below)
+        const uint32_t t = base + threadIdx.x;
+        uint2 v = next;
+        next = t + kCarry < n_tiles ? tiles[t + kCarry] : make_uint2(0u, 0u);
+        for (uint32_t d = 1; d < 64; d <<= 1) {  // inclusive scan within the wave
+            const uint2 p = make_uint2(__shfl_up(v.x, d), __shfl_up(v.y, d));
+            if (lane >= d) v = chain_op(p, v);
+        }
+        if (lane == 63u) s_w[wv] = v;
+        __syncthreads();
+        uint2 pre = run;  // everything before this wave
+        for (uint32_t w = 0; w < wv; w++) pre = chain_op(pre, s_w[w]);
+        const uint2 incl = chain_op(pre, v);
+        uint2 excl = make_uint2(__shfl_up(incl.x, 1u), __shfl_up(incl.y, 1u));
+        if (lane == 0) excl = pre;
+        if (t < n_tiles) tiles[t] = excl;
+        if (threadIdx.x == kCarry - 1) s_total = incl;
+        __syncthreads();
+        run = s_total;
+    }
+    if (threadIdx.x == 0) *n_frames = run.x;
+}
+
+struct ChainFrames {  // the scratch infw_frame_batch and the map back
+    uint64_t *offsets;
+    uint32_t *linear_len, *pkt_len, *ifindex, *frame_of;
+};
+
+__global__ __launch_bounds__(kTile) void xdp_chain_emit(const infw_xdp_desc *__restrict__ descs, uint64_t n,
+                                                         const uint2 *__restrict__ tiles,
+                                                         const uint32_t *__restrict__ n_frames, uint32_t ifindex,
+                                                         ChainFrames out) {
+    __shared__ uint2 s_w[kWaves];
+    const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+    const LaneScan s = scan_wave(descs, i, n);
+    if ((threadIdx.x & 63u) == 63u) s_w[threadIdx.x >> 6] = make_uint2(s.wheads, s.sum);
+    __syncthreads();
+    uint2 pre = tiles[blockIdx.x];  // {frames before the tile, length of the chain open at its start}
+    for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) pre = chain_op(pre, s_w[w]);
+    if (i >= n) return;
+    // descriptor 0 is a head, so pre.x + s.heads >= 1
+    const uint32_t frame = pre.x + s.heads - 1u;
+    out.frame_of[i] = frame;
+    out.ifindex[i] = ifindex;
+    if (i >= *n_frames) {  // a slot no frame owns (frame < n_frames <= i: no head or closer writes it)
+        out.offsets[i] = 0;
+        out.linear_len[i] = 0;
+        out.pkt_len[i] = 0;
+    }
+    if (s.head) {
+        out.offsets[frame] = (s.addr & ((1ull << 48) - 1)) + (s.addr >> 48);
+        out.linear_len[frame] = s.len;
+    }
+    if (!(s.opt & INFW_XDP_PKT_CONTD) || i == n - 1) out.pkt_len[frame] = s.sum + (s.heads ? 0u : pre.y);
+}
+
+__global__ __launch_bounds__(256) void xdp_chain_scatter(const uint32_t *__restrict__ frame_of, uint64_t n,
+                                                          const uint32_t *__restrict__ fres,
+                                                          const uint8_t *__restrict__ fver,
+                                                          uint32_t *__restrict__ results, uint8_t *__restrict__ verdicts) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t f = __builtin_nontemporal_load(&frame_of[i]);
+        if (results) __builtin_nontemporal_store(fres[f], &results[i]);
+        if (verdicts) __builtin_nontemporal_store(fver[f], &verdicts[i]);
+    }
+}
+
+}  // namespace
+
+extern "C" int infw_launch_classify_xdp_mb(const infw_launch_args *a) {
+    const uint64_t n = a->n;
+    if (n == 0) return 0;
+    const uint32_t n_tiles = (uint32_t)((n + kTile - 1) / kTile);  // n < 2^31 (the caller's check)
+    // one stream-ordered allocation from the context's pool, carved at 16-B boundaries: 29 B per descriptor (frame
+    // batch 20, frame_of 4, frame results 4 + 1), 8 B per tile and the frame count
+    size_t bytes = 0;
+    auto carve = [&](size_t sz) {
+        const size_t at = bytes;
+        bytes += (sz + 15) & ~(size_t)15;
+        return at;
+    };
+    const size_t o_off = carve(n * 8), o_lin = carve(n * 4), o_plen = carve(n * 4), o_ifx = carve(n * 4),
+                 o_fof = carve(n * 4), o_res = carve(n * 4), o_ver = carve(n), o_tiles = carve((size_t)n_tiles * 8),
+                 o_nf = carve(4);
+    uint8_t *sc = nullptr;
+    if (!a->pool || hipMallocFromPoolAsync(reinterpret_cast<void **>(&sc), bytes, a->pool, a->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return -ENOMEM;
+    }
+    const ChainFrames cf{reinterpret_cast<uint64_t *>(sc + o_off), reinterpret_cast<uint32_t *>(sc + o_lin),
+                         reinterpret_cast<uint32_t *>(sc + o_plen), reinterpret_cast<uint32_t *>(sc + o_ifx),
+                         reinterpret_cast<uint32_t *>(sc + o_fof)};
+    uint32_t *fres = reinterpret_cast<uint32_t *>(sc + o_res);
+    uint8_t *fver = sc + o_ver;
+    uint2 *tiles = reinterpret_cast<uint2 *>(sc + o_tiles);
+    uint32_t *n_frames = reinterpret_cast<uint32_t *>(sc + o_nf);
+
+    hipLaunchKernelGGL(xdp_chain_reduce, dim3(n_tiles), dim3(kTile), 0, a->stream, a->xdp, n, tiles);
+    hipLaunchKernelGGL(xdp_chain_carry, dim3(1), dim3(kCarry), 0, a->stream, tiles, n_tiles, n_frames);
+    hipLaunchKernelGGL(xdp_chain_emit, dim3(n_tiles), dim3(kTile), 0, a->stream, a->xdp, n, (const uint2 *)tiles,
+                       (const uint32_t *)n_frames, a->xdp_ifindex, cf);
+    int rc = hipGetLastError() == hipSuccess ? 0 : -EIO;
+    if (rc == 0) {
+        const infw_frame_batch fb{a->umem, cf.offsets, 0, cf.linear_len, cf.pkt_len, cf.ifindex};
+        infw_launch_args f = *a;
+        f.input = INFW_INPUT_FRAMES;
+        f.frames = &fb;
+        f.umem = nullptr;
+        f.xdp = nullptr;
+        f.results = a->results ? fres : nullptr;
+        f.verdicts = a->verdicts ? fver : nullptr;
+        rc = infw_launch_classify(&f);
+    }
+    if (rc == 0 && (a->results || a->verdicts)) {
+        const uint64_t blocks = (n + 255) / 256, cap = (uint64_t)a->cus * 8;
+        hipLaunchKernelGGL(xdp_chain_scatter, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(256), 0, a->stream,
+                           (const uint32_t *)cf.frame_of, n, (const uint32_t *)fres, (const uint8_t *)fver, a->results,
+                           a->verdicts);
+        if (hipGetLastError() != hipSuccess) rc = -EIO;
+    }
+    (void)hipFreeAsync(sc, a->stream);
+    return rc;
+}

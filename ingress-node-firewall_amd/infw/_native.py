@@ -160,13 +160,16 @@ ABI_SYMBOLS = [
     "infw_classify_frames_ex",
     "infw_get_launch", "infw_events_capture", "infw_build_id", "infw_table_export", "infw_table_import",
     "infw_table_delete_batch", "infw_set_option", "infw_get_option", "infw_option_name", "infw_classify_variant",
-    "infw_kernel_variant_name", "infw_classify_xdp", "infw_classify_xdp_host",
+    "infw_kernel_variant_name", "infw_classify_xdp", "infw_classify_xdp_mb", "infw_classify_xdp_host",
     "infw_pack_xdp_host", "infw_launch_counts", "infw_xdp_host_events", "infw_classify_bursts_host",
     "infw_pack_burst_host", "infw_burst_host_events",
 ]
 ABI_VERSION = 4  # include/infw.h INFW_ABI_VERSION
 INPUT_SOA, INPUT_COMPACT, INPUT_FRAMES, INPUT_XDP = 0, 1, 2, 3  # INFW_INPUT_*
 VARIANT_EVENTS = 0x1  # INFW_VARIANT_EVENTS
+XDP_PKT_CONTD = 1  # INFW_XDP_PKT_CONTD (linux/if_xdp.h): the frame continues in the next descriptor
+# csrc/infw_launch.h: descriptors per workgroup of infw_classify_xdp_mb's chain pass, tile summaries per carry round
+XDP_CHAIN_TILE, XDP_CHAIN_CARRY = 256, 512
 
 
 # torch (device memory, streams, RCCL) ships its own libamdhip64.so.7; loading it
@@ -253,6 +256,8 @@ _sig = {
     "infw_burst_host_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "infw_classify_xdp": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infw_classify_xdp_mb": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "infw_classify_xdp_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64]),
     "infw_pack_xdp_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, P(BatchSoaC)]),
 }

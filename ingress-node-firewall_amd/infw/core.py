@@ -349,6 +349,22 @@ class Classifier:
                                       results.data_ptr() if results is not None else None,
                                       verdicts.data_ptr() if verdicts is not None else None, sp), "classify_xdp")
 
+    def classify_xdp_mb(self, umem, descs, n: int, ifindex: int, results=None, verdicts=None, dev: int = 0,
+                        stream=None) -> None:
+        """infw_classify_xdp_mb: the ring of a socket bound with XDP_USE_SG — one frame per descriptor chain (a head
+        and the descriptors after it up to the first with XDP_PKT_CONTD clear), classified on the head's bytes with
+        the chain's summed length and counted once; `results` / `verdicts` stay per descriptor, every descriptor of
+        a chain receiving its frame's.  Arguments as classify_xdp."""
+        if stream is None:
+            import torch
+            on = results.device if results is not None and results.is_cuda else torch.device("cuda", dev)
+            stream = torch.cuda.current_stream(on)
+        sp = stream if isinstance(stream, int) else stream.cuda_stream
+        check(N.lib.infw_classify_xdp_mb(self._ctx, dev, umem.data_ptr(), descs.data_ptr(), n, ifindex,
+                                         results.data_ptr() if results is not None else None,
+                                         verdicts.data_ptr() if verdicts is not None else None, sp),
+              "classify_xdp_mb")
+
     def classify_xdp_host(self, rings, chunk: int = 0, dev: int = 0) -> None:
         """infw_classify_xdp_host: AF_XDP RX rings over a host umem, packed on the context's host threads and
         classified through the device (synchronous).  `rings`: (umem, descs, n, ifindex, results, verdicts) per
