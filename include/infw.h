@@ -387,17 +387,20 @@ int infw_classify_xdp(infw_ctx *ctx, int dev, const uint8_t *umem, const struct 
 /*     head's len, frame length (bpf_xdp_get_buff_len(), the counters' bytes,  */
 /*     kernel.c:446, :450) = the sum of the chain's len, modulo 2^32;          */
 /*   - it is counted once in the per-rule counters;                            */
-/*   - a continuation descriptor's addr is never dereferenced;                 */
+/*   - a continuation descriptor's addr is never dereferenced (the one call    */
+/*     that reads a continuation's bytes is infw_events_capture_xdp, below);   */
 /*   - every descriptor of the chain receives the head's result word and       */
 /*     verdict (result_words[i] / xdp_verdicts[i] stay per descriptor, so each */
 /*     buffer can be released or forwarded);                                   */
 /*   - other options bits are ignored.                                         */
 /* With every options == 0 it computes what infw_classify_xdp computes.        */
 /* Memory checks, alignment and errnos as infw_classify_xdp; -EINVAL for       */
-/* n >= 2^31, -ENOMEM when the per-call scratch (29 B per descriptor, stream-  */
-/* ordered from the context's pool) cannot be had.  Asynchronous on `stream`.  */
-/* No deny-event stream.  The host-fed calls below are single-buffer (they     */
-/* ignore options, as infw_classify_xdp does).                                 */
+/* n >= 2^31, -ENOMEM when the per-call scratch (29 B per descriptor, 33 B     */
+/* with the event stream of infw_classify_xdp_mb_ex; stream-ordered from the   */
+/* context's pool) cannot be had.  Asynchronous on `stream`.  Deny events:     */
+/* infw_classify_xdp_mb_ex (declared with the sidebands below).  The host-fed  */
+/* calls below are single-buffer (they ignore options, as infw_classify_xdp    */
+/* does).                                                                      */
 #define INFW_XDP_PKT_CONTD (1u << 0)   /* linux/if_xdp.h XDP_PKT_CONTD */
 int infw_classify_xdp_mb(infw_ctx *ctx, int dev, const uint8_t *umem, const struct infw_xdp_desc *descs, uint64_t n,
                          uint32_t ifindex, uint32_t *result_words, uint8_t *xdp_verdicts, void *stream);
@@ -471,6 +474,23 @@ int infw_classify_frames_ex(infw_ctx *ctx, int dev, const struct infw_frame_batc
                             uint32_t *result_words, uint8_t *xdp_verdicts,
                             const struct infw_classify_ex *ex, void *stream);
 
+/* infw_classify_xdp_mb with the sidebands; ex == NULL is infw_classify_xdp_mb */
+/* itself (same result words, verdicts and counters either way).  With         */
+/* ex->events it appends one record per frame (descriptor chain) a rule        */
+/* denies, with infw_classify_frames_ex's discipline (one atomic per wave,     */
+/* order across waves unspecified, *events_count counts past events_cap):      */
+/* hdr.ifId = (u16)ifindex, hdr.ruleId, hdr.action = 1, hdr.pktLength =        */
+/* (u16)(sum of the chain's len) — bpf_xdp_get_buff_len(), kernel.c:372 —,     */
+/* captured = min(sum, 256), and pkt_index = the RING index of the frame's     */
+/* head descriptor, which is what infw_events_capture_xdp takes.  Records      */
+/* already in the buffer (below *events_count at the call) are not touched.    */
+/* A ring whose options are all 0 is a single-buffer ring: this is the event   */
+/* stream of infw_classify_xdp too.  ex is validated as in                     */
+/* infw_classify_frames_ex (-EINVAL); other errnos as infw_classify_xdp_mb.    */
+int infw_classify_xdp_mb_ex(infw_ctx *ctx, int dev, const uint8_t *umem, const struct infw_xdp_desc *descs,
+                            uint64_t n, uint32_t ifindex, uint32_t *result_words, uint8_t *xdp_verdicts,
+                            const struct infw_classify_ex *ex, void *stream);
+
 /*  - Deny-event payload: the perf sample each record stands for, as the      */
 /*    reader receives it (kernel.c:392-399: bpf_perf_event_output(ctx, map,   */
 /*    BPF_F_CURRENT_CPU | min(len, 256) << 32, &hdr, 8); events.go:77-96       */
@@ -495,6 +515,28 @@ struct infw_event_sample {
 int infw_events_capture(infw_ctx *ctx, int dev, const struct infw_frame_batch *frames, uint64_t n_frames,
                         const struct infw_event_rec *events, uint64_t events_cap,
                         const uint64_t *events_count, struct infw_event_sample *samples, void *stream);
+
+/* The same for the records of infw_classify_xdp_mb_ex over the same ring: the */
+/* reference program is SEC("xdp.frags") and bpf_perf_event_output copies the  */
+/* sample's bytes across the frame's fragments, so slot k holds the first      */
+/* `captured` bytes of the CONCATENATION of the chain's buffers, in            */
+/* infw_events_capture's layout (size word, header, bytes, zeros to 272).  The */
+/* chain is descriptor h = pkt_index and the descriptors after it, up to and   */
+/* including the first with PKT_CONTD clear, or n-1.  Frame byte b is byte     */
+/* b - S_j of descriptor j, where S_j is the sum of len over h..j-1 and        */
+/* S_j <= b < S_j + len_j, read at                                             */
+/* umem + (addr_j & (2^48-1)) + (addr_j >> 48) + (b - S_j).  Zero-length       */
+/* descriptors contribute nothing.  A record with pkt_index >= n (a record of  */
+/* another batch) gets its size and header and no frame bytes.  No byte        */
+/* outside [buffer_j, buffer_j + len_j) of a chain member and no descriptor at */
+/* index >= n is read, and the walk stops once `captured` bytes are placed.    */
+/* This is the one call that dereferences a continuation descriptor's addr.    */
+/* Stream-ordered after the classify (the count is read on the device).        */
+/* Memory checks, alignment and -EFAULT as infw_classify_xdp_mb; samples:      */
+/* device memory of events_cap slots, 8-byte aligned.                          */
+int infw_events_capture_xdp(infw_ctx *ctx, int dev, const uint8_t *umem, const struct infw_xdp_desc *descs,
+                            uint64_t n, const struct infw_event_rec *events, uint64_t events_cap,
+                            const uint64_t *events_count, struct infw_event_sample *samples, void *stream);
 
 /* Host-resident batch: the SoA streams, result words and verdicts live in   */
 /* host memory (as a cgo caller hands them over).  The batch goes through    */

@@ -55,7 +55,14 @@ int infw_launch_shape_ok(int block, int group, int blocks_per_cu);
 // one frame per descriptor chain in scratch from a->pool, classified by infw_launch_classify as INFW_INPUT_FRAMES
 // (a->input is ignored) and the answers scattered to a->results / a->verdicts per descriptor.  Asynchronous.
 // 0, -EIO on a launch error, -ENOMEM when there is no pool or the scratch cannot be allocated.
+// With a->ev_count the frames kernel's event instantiation appends the deny records, and the records this call
+// appended get pkt_index = the ring index of the frame's head descriptor (infw_classify_xdp_mb_ex).
 int infw_launch_classify_xdp_mb(const infw_launch_args *a);
+// infw_events_capture_xdp (xdpchain.hip): samples[k] for k < min(*count, cap), each record's first `captured` frame
+// bytes gathered across the descriptor chain that starts at its pkt_index.  Asynchronous.  0, -EIO.
+int infw_launch_event_samples_xdp(const uint8_t *umem, const infw_xdp_desc *descs, uint64_t n,
+                                  const infw_event_rec *ev, uint64_t cap, const uint64_t *count,
+                                  infw_event_sample *samples, uint32_t cus, hipStream_t stream);
 }
 // The chain pass's tiling: descriptors per workgroup of the reduce / emit kernels, tile summaries per round of the
 // carry kernel (infw/_native.py mirrors them for the tests' ring shapes).

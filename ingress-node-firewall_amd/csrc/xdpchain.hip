@@ -19,7 +19,14 @@
 //
 // Within a wave the head mask is one ballot; a lane's distance to its chain's head follows from the mask by clz, and
 // the segmented sum is a DPP scan (row_shr 1/2/4/8, row_bcast 15/31) whose every step is guarded by that distance.
-// The waves of a tile are combined through LDS.  A continuation's addr is never used.
+// The waves of a tile are combined through LDS.  The classify never uses a continuation's addr.
+//
+// Deny events (infw_classify_xdp_mb_ex): the frames kernel's event instantiation appends its records with the scratch
+// frame index; xdp_chain_emit also writes head_of[frame] and snapshots *events_count, and xdp_event_remap rewrites
+// pkt_index to the head's ring index for the records this call appended, and for no other.
+//
+//   xdp_event_samples_kernel   infw_events_capture_xdp: the perf sample of each record, its first `captured` bytes
+//                      gathered across the chain's buffers — the one place a continuation's addr is dereferenced
 #include <hip/hip_runtime.h>
 #include <errno.h>
 #include <stdint.h>
@@ -145,6 +152,9 @@ __global__ __launch_bounds__(kCarry) void xdp_chain_carry(uint2 *__restrict__ ti
 struct ChainFrames {  // the scratch infw_frame_batch and the map back
     uint64_t *offsets;
     uint32_t *linear_len, *pkt_len, *ifindex, *frame_of;
+    uint32_t *head_of;           // events only (else null): a frame's head descriptor
+    const uint64_t *ev_count;    // events only: the caller's event count, copied to *ev_before ahead of the classify
+    uint64_t *ev_before;
 };
 
 __global__ __launch_bounds__(kTile) void xdp_chain_emit(const infw_xdp_desc *__restrict__ descs, uint64_t n,
@@ -159,6 +169,7 @@ __global__ __launch_bounds__(kTile) void xdp_chain_emit(const infw_xdp_desc *__r
     uint2 pre = tiles[blockIdx.x];  // {frames before the tile, length of the chain open at its start}
     for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) pre = chain_op(pre, s_w[w]);
     if (i >= n) return;
+    if (i == 0 && out.ev_before) *out.ev_before = *out.ev_count;
     // descriptor 0 is a head, so pre.x + s.heads >= 1
     const uint32_t frame = pre.x + s.heads - 1u;
     out.frame_of[i] = frame;
@@ -171,6 +182,7 @@ __global__ __launch_bounds__(kTile) void xdp_chain_emit(const infw_xdp_desc *__r
     if (s.head) {
         out.offsets[frame] = (s.addr & ((1ull << 48) - 1)) + (s.addr >> 48);
         out.linear_len[frame] = s.len;
+        if (out.head_of) out.head_of[frame] = (uint32_t)i;
     }
     if (!(s.opt & INFW_XDP_PKT_CONTD) || i == n - 1) out.pkt_len[frame] = s.sum + (s.heads ? 0u : pre.y);
 }
@@ -187,14 +199,133 @@ __global__ __launch_bounds__(256) void xdp_chain_scatter(const uint32_t *__restr
     }
 }
 
+// The records the frames kernel appended during this call — slots [*before, min(*count, cap)) — carry the scratch
+// frame index: rewrite it to the ring index of the frame's head.  Records that were in the buffer before are not read.
+__global__ __launch_bounds__(256) void xdp_event_remap(infw_event_rec *__restrict__ ev, uint64_t cap,
+                                                        const uint64_t *__restrict__ before,
+                                                        const uint64_t *__restrict__ count,
+                                                        const uint32_t *__restrict__ head_of, uint64_t n) {
+    const uint64_t c = *count, end = c < cap ? c : cap;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t k = *before + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < end; k += stride) {
+        const uint64_t f = ev[k].pkt_index;
+        if (f < n) ev[k].pkt_index = head_of[f];  // always true for a record of this call (f < frames <= n)
+    }
+}
+
+// ---- infw_events_capture_xdp: perf samples gathered across a chain's buffers ------------------------------------
+//
+// One wave per event record, kSampleWaves records per workgroup, grid-stride over min(*count, cap).  The wave builds
+// the record's 272-B slot in its own LDS image and stores it as 34 8-byte words:
+//   walk   64 descriptors per round from the head h = pkt_index: lane l loads descriptor h + 64 r + l (one 16-B load,
+//          only below n); the chain ends at the first lane with PKT_CONTD clear or index n - 1 (ballot + ctz).  The
+//          lens up to there, each clamped to the 256 bytes a sample can hold (the sums cannot wrap, and nothing behind
+//          a clamped descriptor is wanted), go through an unsegmented inclusive DPP scan; with the bytes covered by
+//          earlier rounds that is each descriptor's start S in the frame.  A lane is live when [S, S + len) meets
+//          [0, captured).  Rounds go on while the chain is open and fewer than `captured` bytes are covered.
+//   copy   wave-uniform loop over the live mask: source pointer, S and byte count of fragment j by readlane, then all
+//          64 lanes copy it coalesced (lane t takes bytes t, t + 64, ...) to image[12 + S + t]; at most 256 bytes per
+//          record however the frame is cut.  Only [buffer_j, buffer_j + min(len_j, captured - S_j)) is read.
+//   out    the image is zeroed before the walk (so the pad, and the frame bytes of a record whose chain is not in
+//          this ring or is shorter than `captured`, are zeros), size and header go in last; lanes 0..33 read their
+//          word back (ds_read_b64) and store it.  The hand-offs through LDS are within one wave: wave-scope fences,
+//          no workgroup barrier (the waves of a workgroup run different numbers of records and rounds).
+constexpr int kSampleWaves = 4;
+constexpr uint32_t kSampleWords = INFW_EVENT_SAMPLE_BYTES / 8;
+static_assert(INFW_EVENT_SAMPLE_BYTES % 8 == 0 && kSampleWords <= 64 && INFW_MAX_EVENT_DATA + 12 <= INFW_EVENT_SAMPLE_BYTES,
+              "one wave per slot");
+
+__device__ __forceinline__ void wave_lds_handoff() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {  // unsegmented: the ladder of scan_wave, unguarded
+    x += dpp0<kRowShr + 1, 0xF>(x);
+    x += dpp0<kRowShr + 2, 0xF>(x);
+    x += dpp0<kRowShr + 4, 0xF>(x);
+    x += dpp0<kRowShr + 8, 0xF>(x);
+    x += dpp0<kRowBcast15, 0xA>(x);
+    x += dpp0<kRowBcast31, 0xC>(x);
+    return x;
+}
+
+__global__ __launch_bounds__(64 * kSampleWaves) void xdp_event_samples_kernel(
+    const uint8_t *__restrict__ umem, const infw_xdp_desc *__restrict__ descs, uint64_t n,
+    const infw_event_rec *__restrict__ ev, uint64_t cap, const uint64_t *__restrict__ count,
+    uint8_t *__restrict__ out) {
+    __shared__ uint64_t s_img[kSampleWaves][kSampleWords];
+    const uint64_t c = *count, n_rec = c < cap ? c : cap;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // the record is wave-uniform
+    uint64_t *const img8 = s_img[wv];
+    uint8_t *const img = reinterpret_cast<uint8_t *>(img8);
+    const uint64_t waves = (uint64_t)gridDim.x * kSampleWaves;
+    for (uint64_t r = (uint64_t)blockIdx.x * kSampleWaves + wv; r < n_rec; r += waves) {
+        const infw_event_rec e = ev[r];
+        const uint64_t h = e.pkt_index;
+        const uint32_t captured = e.captured < INFW_MAX_EVENT_DATA ? e.captured : INFW_MAX_EVENT_DATA;
+        if (lane < kSampleWords) img8[lane] = 0;
+        wave_lds_handoff();
+        uint32_t covered = 0;  // frame bytes the descriptors of earlier rounds hold (clamped: >= captured ends the walk)
+        bool open = h < n;     // a record of another batch: size and header only
+        for (uint64_t at = h; open && covered < captured; at += 64) {
+            const uint64_t i = at + lane;
+            uint64_t addr = 0;
+            uint32_t len = 0, opt = 0;
+            if (i < n) {
+                const u32x4 d = *(reinterpret_cast<const u32x4 *>(descs) + i);
+                addr = (uint64_t)d[1] << 32 | d[0];
+                len = d[2];
+                opt = d[3];
+            }
+            // lanes at or past n close the chain too, so nothing behind the ring's end is summed (i == n - 1 is first)
+            const uint64_t ends = __ballot(i + 1 >= n || !(opt & INFW_XDP_PKT_CONTD));
+            const uint32_t last = ends ? (uint32_t)__builtin_ctzll(ends) : 63u;
+            open = ends == 0;
+            const uint32_t l = lane <= last ? (len < INFW_MAX_EVENT_DATA ? len : INFW_MAX_EVENT_DATA) : 0u;
+            const uint32_t incl = wave_scan_incl(l);
+            const uint32_t S = covered + incl - l;
+            uint64_t live = __ballot(l != 0 && S < captured);
+            const uint64_t src = (addr & ((1ull << 48) - 1)) + (addr >> 48);
+            while (live) {  // wave-uniform
+                const int j = __builtin_ctzll(live);
+                live &= live - 1;
+                const uint64_t sj = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(src >> 32), j) << 32 |
+                                    (uint32_t)__builtin_amdgcn_readlane((int)src, j);
+                const uint32_t Sj = (uint32_t)__builtin_amdgcn_readlane((int)S, j);
+                const uint32_t lj = (uint32_t)__builtin_amdgcn_readlane((int)l, j);
+                const uint32_t room = captured - Sj, cnt = lj < room ? lj : room;  // Sj < captured <= 256
+                const uint8_t *__restrict__ f = umem + sj;
+                for (uint32_t b = lane; b < cnt; b += 64) img[12u + Sj + b] = f[b];
+            }
+            covered += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+        if (lane == 0) {
+            uint32_t hw[2];
+            __builtin_memcpy(hw, &e.hdr, 8);
+            uint32_t *const img4 = reinterpret_cast<uint32_t *>(img);
+            img4[0] = ((8u + e.captured + 4u + 7u) & ~7u) - 4u;  // perf's raw size, as event_samples_kernel writes it
+            img4[1] = hw[0];
+            img4[2] = hw[1];
+        }
+        wave_lds_handoff();
+        if (lane < kSampleWords) reinterpret_cast<uint64_t *>(out + r * INFW_EVENT_SAMPLE_BYTES)[lane] = img8[lane];
+        wave_lds_handoff();  // the next record rewrites the image
+    }
+}
+
 }  // namespace
 
 extern "C" int infw_launch_classify_xdp_mb(const infw_launch_args *a) {
     const uint64_t n = a->n;
     if (n == 0) return 0;
     const uint32_t n_tiles = (uint32_t)((n + kTile - 1) / kTile);  // n < 2^31 (the caller's check)
+    const bool events = a->ev_count != nullptr;
     // one stream-ordered allocation from the context's pool, carved at 16-B boundaries: 29 B per descriptor (frame
-    // batch 20, frame_of 4, frame results 4 + 1), 8 B per tile and the frame count
+    // batch 20, frame_of 4, frame results 4 + 1), 8 B per tile and the frame count; with the event stream 4 B more
+    // per descriptor (head_of) and the count's snapshot
     size_t bytes = 0;
     auto carve = [&](size_t sz) {
         const size_t at = bytes;
@@ -203,15 +334,17 @@ extern "C" int infw_launch_classify_xdp_mb(const infw_launch_args *a) {
     };
     const size_t o_off = carve(n * 8), o_lin = carve(n * 4), o_plen = carve(n * 4), o_ifx = carve(n * 4),
                  o_fof = carve(n * 4), o_res = carve(n * 4), o_ver = carve(n), o_tiles = carve((size_t)n_tiles * 8),
-                 o_nf = carve(4);
+                 o_nf = carve(4), o_hof = carve(events ? n * 4 : 0), o_evb = carve(events ? 8 : 0);
     uint8_t *sc = nullptr;
     if (!a->pool || hipMallocFromPoolAsync(reinterpret_cast<void **>(&sc), bytes, a->pool, a->stream) != hipSuccess) {
         (void)hipGetLastError();
         return -ENOMEM;
     }
+    uint32_t *head_of = events ? reinterpret_cast<uint32_t *>(sc + o_hof) : nullptr;
+    uint64_t *ev_before = events ? reinterpret_cast<uint64_t *>(sc + o_evb) : nullptr;
     const ChainFrames cf{reinterpret_cast<uint64_t *>(sc + o_off), reinterpret_cast<uint32_t *>(sc + o_lin),
                          reinterpret_cast<uint32_t *>(sc + o_plen), reinterpret_cast<uint32_t *>(sc + o_ifx),
-                         reinterpret_cast<uint32_t *>(sc + o_fof)};
+                         reinterpret_cast<uint32_t *>(sc + o_fof), head_of, a->ev_count, ev_before};
     uint32_t *fres = reinterpret_cast<uint32_t *>(sc + o_res);
     uint8_t *fver = sc + o_ver;
     uint2 *tiles = reinterpret_cast<uint2 *>(sc + o_tiles);
@@ -223,6 +356,7 @@ extern "C" int infw_launch_classify_xdp_mb(const infw_launch_args *a) {
                        (const uint32_t *)n_frames, a->xdp_ifindex, cf);
     int rc = hipGetLastError() == hipSuccess ? 0 : -EIO;
     if (rc == 0) {
+        // a->ev / ev_cap / ev_count go with the copy: the frames kernel's event instantiation appends the records
         const infw_frame_batch fb{a->umem, cf.offsets, 0, cf.linear_len, cf.pkt_len, cf.ifindex};
         infw_launch_args f = *a;
         f.input = INFW_INPUT_FRAMES;
@@ -233,6 +367,13 @@ extern "C" int infw_launch_classify_xdp_mb(const infw_launch_args *a) {
         f.verdicts = a->verdicts ? fver : nullptr;
         rc = infw_launch_classify(&f);
     }
+    if (rc == 0 && events && a->ev_cap) {  // at most one new record per frame, and none past the capacity
+        const uint64_t most = n < a->ev_cap ? n : a->ev_cap, blocks = (most + 255) / 256, cap = (uint64_t)a->cus * 8;
+        hipLaunchKernelGGL(xdp_event_remap, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(256), 0, a->stream,
+                           a->ev, a->ev_cap, (const uint64_t *)ev_before, (const uint64_t *)a->ev_count,
+                           (const uint32_t *)head_of, n);
+        if (hipGetLastError() != hipSuccess) rc = -EIO;
+    }
     if (rc == 0 && (a->results || a->verdicts)) {
         const uint64_t blocks = (n + 255) / 256, cap = (uint64_t)a->cus * 8;
         hipLaunchKernelGGL(xdp_chain_scatter, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(256), 0, a->stream,
@@ -242,4 +383,15 @@ extern "C" int infw_launch_classify_xdp_mb(const infw_launch_args *a) {
     }
     (void)hipFreeAsync(sc, a->stream);
     return rc;
+}
+
+// One wave per record: kSampleWaves records per workgroup, the grid capped by the CU count (grid-stride beyond it).
+extern "C" int infw_launch_event_samples_xdp(const uint8_t *umem, const infw_xdp_desc *descs, uint64_t n,
+                                             const infw_event_rec *ev, uint64_t cap, const uint64_t *count,
+                                             infw_event_sample *samples, uint32_t cus, hipStream_t stream) {
+    if (cap == 0) return 0;
+    const uint64_t blocks = (cap + kSampleWaves - 1) / kSampleWaves, lim = 8ull * cus;
+    hipLaunchKernelGGL(xdp_event_samples_kernel, dim3((uint32_t)(blocks < lim ? blocks : lim)), dim3(64 * kSampleWaves),
+                       0, stream, umem, descs, n, ev, cap, count, reinterpret_cast<uint8_t *>(samples));
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }

@@ -160,7 +160,8 @@ ABI_SYMBOLS = [
     "infw_classify_frames_ex",
     "infw_get_launch", "infw_events_capture", "infw_build_id", "infw_table_export", "infw_table_import",
     "infw_table_delete_batch", "infw_set_option", "infw_get_option", "infw_option_name", "infw_classify_variant",
-    "infw_kernel_variant_name", "infw_classify_xdp", "infw_classify_xdp_mb", "infw_classify_xdp_host",
+    "infw_kernel_variant_name", "infw_classify_xdp", "infw_classify_xdp_mb", "infw_classify_xdp_mb_ex",
+    "infw_events_capture_xdp", "infw_classify_xdp_host",
     "infw_pack_xdp_host", "infw_launch_counts", "infw_xdp_host_events", "infw_classify_bursts_host",
     "infw_pack_burst_host", "infw_burst_host_events",
 ]
@@ -258,6 +259,10 @@ _sig = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "infw_classify_xdp_mb": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infw_classify_xdp_mb_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, P(ClassifyEx), C.c_void_p]),
+    "infw_events_capture_xdp": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                          C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infw_classify_xdp_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64]),
     "infw_pack_xdp_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, P(BatchSoaC)]),
 }

@@ -350,20 +350,40 @@ class Classifier:
                                       verdicts.data_ptr() if verdicts is not None else None, sp), "classify_xdp")
 
     def classify_xdp_mb(self, umem, descs, n: int, ifindex: int, results=None, verdicts=None, dev: int = 0,
-                        stream=None) -> None:
+                        stream=None, *, events=None, events_count=None) -> None:
         """infw_classify_xdp_mb: the ring of a socket bound with XDP_USE_SG — one frame per descriptor chain (a head
         and the descriptors after it up to the first with XDP_PKT_CONTD clear), classified on the head's bytes with
         the chain's summed length and counted once; `results` / `verdicts` stay per descriptor, every descriptor of
-        a chain receiving its frame's.  Arguments as classify_xdp."""
+        a chain receiving its frame's.  Arguments as classify_xdp.  events / events_count: the deny-event stream as
+        in classify_frames (infw_classify_xdp_mb_ex); a record's pkt_index is the ring index of its frame's head."""
         if stream is None:
             import torch
             on = results.device if results is not None and results.is_cuda else torch.device("cuda", dev)
             stream = torch.cuda.current_stream(on)
         sp = stream if isinstance(stream, int) else stream.cuda_stream
-        check(N.lib.infw_classify_xdp_mb(self._ctx, dev, umem.data_ptr(), descs.data_ptr(), n, ifindex,
-                                         results.data_ptr() if results is not None else None,
-                                         verdicts.data_ptr() if verdicts is not None else None, sp),
-              "classify_xdp_mb")
+        ex = None
+        if events is not None:
+            ex = N.ClassifyEx(C.sizeof(N.ClassifyEx), 0, events.data_ptr(), events.numel() // C.sizeof(N.EventRec),
+                              events_count.data_ptr())
+        check(N.lib.infw_classify_xdp_mb_ex(self._ctx, dev, umem.data_ptr(), descs.data_ptr(), n, ifindex,
+                                            results.data_ptr() if results is not None else None,
+                                            verdicts.data_ptr() if verdicts is not None else None,
+                                            C.byref(ex) if ex is not None else None, sp), "classify_xdp_mb")
+
+    def events_capture_xdp(self, umem, descs, n: int, events, events_count, samples, dev: int = 0,
+                           stream=None) -> None:
+        """infw_events_capture_xdp: the perf samples of the deny events classify_xdp_mb(events=...) wrote for the
+        same ring, each frame's first min(length, 256) bytes gathered across its chain's buffers.  `samples`: uint8
+        device tensor of (events capacity) x 272 B, as for events_capture."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(samples.device)
+        sp = stream if isinstance(stream, int) else stream.cuda_stream
+        cap = events.numel() // C.sizeof(N.EventRec)
+        assert samples.numel() >= cap * N.EVENT_SAMPLE_BYTES, "samples: one 272-B slot per event record"
+        check(N.lib.infw_events_capture_xdp(self._ctx, dev, umem.data_ptr(), descs.data_ptr(), n, events.data_ptr(),
+                                            cap, events_count.data_ptr(), samples.data_ptr(), sp),
+              "events_capture_xdp")
 
     def classify_xdp_host(self, rings, chunk: int = 0, dev: int = 0) -> None:
         """infw_classify_xdp_host: AF_XDP RX rings over a host umem, packed on the context's host threads and
