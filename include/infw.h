@@ -16,7 +16,8 @@
  *     infw_table_import/export, infw_stats_reset, infw_set_option,
  *     infw_set_launch, infw_debug_lookup_set, infw_debug_keys_clear) are
  *     externally serialised, like ebpfsyncer.go:62,72-73 (e.mu).  The data
- *     path and the readers — infw_classify*, infw_pack_frames*,
+ *     path and the readers — infw_classify* (infw_classify_xdp_rings
+ *     among them), infw_pack_frames*,
  *     infw_events_capture, infw_stats_read*, infw_table_info,
  *     infw_debug_walk, infw_debug_keys_read, infw_classify_variant — may run
  *     on any number of other threads concurrently with them and with each
@@ -398,9 +399,9 @@ int infw_classify_xdp(infw_ctx *ctx, int dev, const uint8_t *umem, const struct 
 /* n >= 2^31, -ENOMEM when the per-call scratch (29 B per descriptor, 33 B     */
 /* with the event stream of infw_classify_xdp_mb_ex; stream-ordered from the   */
 /* context's pool) cannot be had.  Asynchronous on `stream`.  Deny events:     */
-/* infw_classify_xdp_mb_ex (declared with the sidebands below).  The host-fed  */
-/* calls below are single-buffer (they ignore options, as infw_classify_xdp    */
-/* does).                                                                      */
+/* infw_classify_xdp_mb_ex (declared with the sidebands below).  Every ring of  */
+/* a poll in one call: infw_classify_xdp_rings, below.  The host-fed calls     */
+/* below are single-buffer (they ignore options, as infw_classify_xdp does).   */
 #define INFW_XDP_PKT_CONTD (1u << 0)   /* linux/if_xdp.h XDP_PKT_CONTD */
 int infw_classify_xdp_mb(infw_ctx *ctx, int dev, const uint8_t *umem, const struct infw_xdp_desc *descs, uint64_t n,
                          uint32_t ifindex, uint32_t *result_words, uint8_t *xdp_verdicts, void *stream);
@@ -431,6 +432,42 @@ struct infw_xdp_ring {
 };
 int infw_classify_xdp_host(infw_ctx *ctx, int dev, const struct infw_xdp_ring *rings, uint32_t n_rings,
                            uint64_t chunk);
+/* The device-read path over every ring of a poll (one socket per NIC queue,   */
+/* several queues per interface, several interfaces) in one call: what         */
+/*   infw_classify_xdp_mb(ctx, dev, rings[r].umem, rings[r].descs, rings[r].n, */
+/*                        rings[r].ifindex, rings[r].results,                  */
+/*                        rings[r].verdicts, stream)                           */
+/* computes for r = 0 .. n_rings-1 on one stream against one table epoch —     */
+/* result words, verdicts and counters — with one scratch allocation and one   */
+/* set of launches for all of them.  One frame per descriptor chain, classified */
+/* on the head's bytes with the chain's summed length and counted once; every  */
+/* descriptor receives its frame's result word and verdict.                    */
+/*   - descriptor 0 of every ring is a head; a chain still open at a ring's    */
+/*     last descriptor ends there: no descriptor of another ring is read or    */
+/*     summed for it;                                                          */
+/*   - a continuation's addr is never dereferenced;                            */
+/*   - rings with n == 0 are skipped; a ring's NULL results or verdicts is     */
+/*     skipped for that ring only;                                             */
+/*   - `rings` is an ordinary host array, read during the call: it may be      */
+/*     reused as soon as the call returns.  The pointers in it are as for      */
+/*     infw_classify_xdp_mb: umem and descs device-accessible (HBM, pinned or  */
+/*     registered host memory), descs 16-byte aligned, results / verdicts      */
+/*     device-writable or NULL;                                                */
+/*   - asynchronous on `stream`; the call does not wait for work already       */
+/*     queued on it.                                                           */
+/* -EINVAL: n_rings > INFW_XDP_RINGS_MAX, a ring's flags != 0, 2^31            */
+/* descriptors or more in all, a NULL or misaligned pointer in a ring with     */
+/* n > 0.  -EFAULT: a ring's umem or descs in memory the GPU cannot read (the  */
+/* check of infw_classify_xdp).  -ENOMEM: no per-call scratch from the         */
+/* context's pool — 29 B per descriptor, 4 B per chunk (64 descriptors of one  */
+/* ring; a ring of n has ceil(n / 64)), 8 B per 4 chunks, 48 B per non-empty   */
+/* ring and 4 B, each array rounded up to 16 B.  -ENODEV: host-only context.   */
+/* Nothing is launched when an error is returned; n_rings == 0 returns 0.      */
+/* No deny events: a caller that needs them calls infw_classify_xdp_mb_ex per  */
+/* ring.                                                                       */
+#define INFW_XDP_RINGS_MAX 1024
+int infw_classify_xdp_rings(infw_ctx *ctx, int dev, const struct infw_xdp_ring *rings, uint32_t n_rings,
+                            void *stream);
 /* The host packer of infw_classify_xdp_host alone, on the calling thread: one */
 /* ring's frames -> the family-compact streams in host memory (the layout       */
 /* infw_classify_c reads; out->ifindex may be NULL, else it is filled with      */

@@ -41,6 +41,18 @@ struct infw_launch_args {
     uint32_t dbg_slots;
 };
 
+// One ring of infw_classify_xdp_rings as the chain pass reads it from its table in scratch: the caller's pointers, and
+// where the ring starts in chunk space (64 descriptors per chunk, no chunk shared by two rings) and in flat
+// descriptor space.  48 B; up to INFW_XDP_RINGS_GROUP of them travel in one upload kernel's arguments.
+struct infw_xdp_ring_ent {
+    const uint8_t *umem;
+    const infw_xdp_desc *descs;
+    uint32_t *results;
+    uint8_t *verdicts;
+    uint32_t n, ifindex, chunk0, flat0;
+};
+#define INFW_XDP_RINGS_GROUP 64
+
 extern "C" {
 // Launch (asynchronous).  0, or -EIO on a launch error.
 int infw_launch_classify(const infw_launch_args *a);
@@ -58,6 +70,12 @@ int infw_launch_shape_ok(int block, int group, int blocks_per_cu);
 // With a->ev_count the frames kernel's event instantiation appends the deny records, and the records this call
 // appended get pkt_index = the ring index of the frame's head descriptor (infw_classify_xdp_mb_ex).
 int infw_launch_classify_xdp_mb(const infw_launch_args *a);
+// infw_classify_xdp_rings (xdpchain.hip): the same for `n_ents` non-empty rings at once — one allocation, one set of
+// launches, one free; no chain runs from one ring into the next.  ents[r].chunk0 / flat0 are the running sums of
+// ceil(n / 64) and n; a->n is the sum of n (< 2^31), n_chunks the sum of the chunks; a->results / verdicts / umem /
+// xdp are ignored (each ring has its own).  `ents` is read before the call returns.  No event stream.  0, -EIO, -ENOMEM.
+int infw_launch_classify_xdp_rings(const infw_launch_args *a, const infw_xdp_ring_ent *ents, uint32_t n_ents,
+                                   uint32_t n_chunks);
 // infw_events_capture_xdp (xdpchain.hip): samples[k] for k < min(*count, cap), each record's first `captured` frame
 // bytes gathered across the descriptor chain that starts at its pkt_index.  Asynchronous.  0, -EIO.
 int infw_launch_event_samples_xdp(const uint8_t *umem, const infw_xdp_desc *descs, uint64_t n,

@@ -27,6 +27,9 @@
 //
 //   xdp_event_samples_kernel   infw_events_capture_xdp: the perf sample of each record, its first `captured` bytes
 //                      gathered across the chain's buffers — the one place a continuation's addr is dereferenced
+//
+// Many rings in one call (infw_classify_xdp_rings): the same passes over 64-descriptor chunks of all the rings, with a
+// ring table and a chunk -> ring map in scratch — the xdp_rings_* kernels below.
 #include <hip/hip_runtime.h>
 #include <errno.h>
 #include <stdint.h>
@@ -316,6 +319,133 @@ __global__ __launch_bounds__(64 * kSampleWaves) void xdp_event_samples_kernel(
     }
 }
 
+// ---- infw_classify_xdp_rings: every ring of a poll through one chain pass ------------------------------------------
+//
+// The unit of work is a chunk: 64 consecutive descriptors of one ring, one wave.  Ring r owns ceil(n_r / 64) consecutive
+// chunks, a workgroup of kRingWaves waves takes kRingWaves consecutive chunks (of one ring or of several), and its
+// summary is the tile summary of the single-ring pass, so xdp_chain_carry runs over it as it is.  Every ring's first
+// chunk has a head at lane 0 and chain_op drops the left length at a head: a chain open at a ring's last descriptor
+// ends there, and frame indices run on across rings.  Frames, frame_of and the frame results live in flat descriptor
+// space (the ring's first flat index + i), which is dense, so the frames kernel runs once over the sum of the n_r.
+//
+//   xdp_rings_upload   the ring table {umem, descs, results, verdicts, n, ifindex, first chunk, first flat index},
+//                      64 entries per launch by value in the kernel arguments: stream-ordered, nothing of the caller's
+//                      is read after the call returns, and no host-side wait
+//   xdp_rings_map      chunk -> ring, one u32 per chunk (binary search of the first-chunk column, once per call;
+//                      the passes below read their ring with one wave-uniform load)
+//   xdp_rings_reduce / xdp_rings_emit / xdp_rings_scatter   the three passes of the single-ring form per chunk; the
+//                      emit writes umem_r - umem_0 + offset (modulo 2^64) for the frames kernel's umem_0 + offset
+constexpr int kRingWaves = 4;  // chunks per workgroup of the reduce / emit / scatter kernels
+constexpr int kRingGroup = INFW_XDP_RINGS_GROUP;
+static_assert(sizeof(infw_xdp_ring_ent) == 48, "three 16-B words per entry");
+
+struct RingGroup {
+    infw_xdp_ring_ent e[kRingGroup];
+};
+
+__global__ __launch_bounds__(kRingGroup) void xdp_rings_upload(const RingGroup g, uint32_t cnt,
+                                                                infw_xdp_ring_ent *__restrict__ table) {
+    if (threadIdx.x < cnt) table[threadIdx.x] = g.e[threadIdx.x];
+}
+
+// The rings of the table are non-empty, so the first-chunk column is strictly increasing: the chunk's ring is the last
+// one that starts at or before it.
+__global__ __launch_bounds__(256) void xdp_rings_map(const infw_xdp_ring_ent *__restrict__ table, uint32_t n_rings,
+                                                      uint32_t n_chunks, uint32_t *__restrict__ chunk_ring) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= n_chunks) return;
+    uint32_t lo = 0, hi = n_rings;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (table[mid].chunk0 <= c) lo = mid;
+        else hi = mid;
+    }
+    chunk_ring[c] = lo;
+}
+
+// The wave's chunk: its ring's entry (wave-uniform) and the lane's ring-relative index.  Past the last chunk the ring
+// is empty (n == 0: scan_wave loads nothing and reports no head), so every lane of the workgroup stays in the scan.
+__device__ __forceinline__ infw_xdp_ring_ent ring_of_chunk(const infw_xdp_ring_ent *__restrict__ table,
+                                                           const uint32_t *__restrict__ chunk_ring, uint32_t c,
+                                                           uint32_t n_chunks, uint64_t &i) {
+    infw_xdp_ring_ent e{};
+    i = threadIdx.x & 63u;
+    if (c < n_chunks) {
+        e = table[__builtin_amdgcn_readfirstlane((int)chunk_ring[c])];
+        i += (uint64_t)(c - e.chunk0) * 64u;
+    }
+    return e;
+}
+
+__global__ __launch_bounds__(64 * kRingWaves) void xdp_rings_reduce(const infw_xdp_ring_ent *__restrict__ table,
+                                                                     const uint32_t *__restrict__ chunk_ring,
+                                                                     uint32_t n_chunks, uint2 *__restrict__ tiles) {
+    __shared__ uint2 s_w[kRingWaves];
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint64_t i;
+    const infw_xdp_ring_ent e = ring_of_chunk(table, chunk_ring, blockIdx.x * kRingWaves + wv, n_chunks, i);
+    const LaneScan s = scan_wave(e.descs, i, e.n);
+    if ((threadIdx.x & 63u) == 63u) s_w[wv] = make_uint2(s.wheads, s.sum);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint2 t = s_w[0];
+        for (int w = 1; w < kRingWaves; w++) t = chain_op(t, s_w[w]);
+        tiles[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(64 * kRingWaves) void xdp_rings_emit(const infw_xdp_ring_ent *__restrict__ table,
+                                                                   const uint32_t *__restrict__ chunk_ring,
+                                                                   uint32_t n_chunks, const uint2 *__restrict__ tiles,
+                                                                   const uint32_t *__restrict__ n_frames,
+                                                                   const uint8_t *umem0, ChainFrames out) {
+    __shared__ uint2 s_w[kRingWaves];
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint64_t i;
+    const infw_xdp_ring_ent e = ring_of_chunk(table, chunk_ring, blockIdx.x * kRingWaves + wv, n_chunks, i);
+    const LaneScan s = scan_wave(e.descs, i, e.n);
+    if ((threadIdx.x & 63u) == 63u) s_w[wv] = make_uint2(s.wheads, s.sum);
+    __syncthreads();
+    uint2 pre = tiles[blockIdx.x];  // {frames before the workgroup's chunks, length of the chain open at their start}
+    for (uint32_t w = 0; w < wv; w++) pre = chain_op(pre, s_w[w]);
+    if (i >= e.n) return;
+    // chunk 0 starts a ring and every ring starts with a head, so pre.x + s.heads >= 1; in a ring's first chunk
+    // s.heads >= 1 on every lane, so the length carried in from the ring before (pre.y) is never added
+    const uint32_t frame = pre.x + s.heads - 1u;
+    const uint64_t g = e.flat0 + i;
+    out.frame_of[g] = frame;
+    if (g >= *n_frames) {  // a slot no frame owns (frame < n_frames <= g: no head or closer writes it)
+        out.offsets[g] = 0;
+        out.linear_len[g] = 0;
+        out.pkt_len[g] = 0;
+        out.ifindex[g] = e.ifindex;
+    }
+    if (s.head) {
+        out.offsets[frame] = (uint64_t)(e.umem - umem0) + (s.addr & ((1ull << 48) - 1)) + (s.addr >> 48);
+        out.linear_len[frame] = s.len;
+        out.ifindex[frame] = e.ifindex;
+    }
+    if (!(s.opt & INFW_XDP_PKT_CONTD) || i == e.n - 1u) out.pkt_len[frame] = s.sum + (s.heads ? 0u : pre.y);
+}
+
+__global__ __launch_bounds__(64 * kRingWaves) void xdp_rings_scatter(const infw_xdp_ring_ent *__restrict__ table,
+                                                                      const uint32_t *__restrict__ chunk_ring,
+                                                                      uint32_t n_chunks,
+                                                                      const uint32_t *__restrict__ frame_of,
+                                                                      const uint32_t *__restrict__ fres,
+                                                                      const uint8_t *__restrict__ fver) {
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t waves = gridDim.x * kRingWaves;
+    for (uint32_t c = blockIdx.x * kRingWaves + wv; c < n_chunks; c += waves) {
+        uint64_t i;
+        const infw_xdp_ring_ent e = ring_of_chunk(table, chunk_ring, c, n_chunks, i);
+        if (i >= e.n) continue;
+        const uint32_t f = __builtin_nontemporal_load(&frame_of[e.flat0 + i]);
+        if (e.results) __builtin_nontemporal_store(fres[f], &e.results[i]);
+        if (e.verdicts) __builtin_nontemporal_store(fver[f], &e.verdicts[i]);
+    }
+}
+
 }  // namespace
 
 extern "C" int infw_launch_classify_xdp_mb(const infw_launch_args *a) {
@@ -379,6 +509,81 @@ extern "C" int infw_launch_classify_xdp_mb(const infw_launch_args *a) {
         hipLaunchKernelGGL(xdp_chain_scatter, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(256), 0, a->stream,
                            (const uint32_t *)cf.frame_of, n, (const uint32_t *)fres, (const uint8_t *)fver, a->results,
                            a->verdicts);
+        if (hipGetLastError() != hipSuccess) rc = -EIO;
+    }
+    (void)hipFreeAsync(sc, a->stream);
+    return rc;
+}
+
+// ents: the call's non-empty rings with their first chunk and first flat index filled in (abi.cpp), read before the
+// call returns; a->n is the sum of their n (< 2^31), n_chunks the sum of their chunks.
+extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const infw_xdp_ring_ent *ents, uint32_t n_ents,
+                                              uint32_t n_chunks) {
+    const uint64_t n = a->n;
+    if (n == 0 || n_ents == 0) return 0;
+    const uint32_t n_tiles = (n_chunks + kRingWaves - 1) / kRingWaves;
+    bool any_res = false, any_ver = false;
+    for (uint32_t r = 0; r < n_ents; r++) any_res |= ents[r].results != nullptr, any_ver |= ents[r].verdicts != nullptr;
+    // one stream-ordered allocation, carved at 16-B boundaries: 29 B per descriptor as for one ring, 4 B per chunk
+    // (its ring), 8 B per workgroup of kRingWaves chunks (its summary), 48 B per ring (the table) and the frame count
+    size_t bytes = 0;
+    auto carve = [&](size_t sz) {
+        const size_t at = bytes;
+        bytes += (sz + 15) & ~(size_t)15;
+        return at;
+    };
+    const size_t o_off = carve(n * 8), o_lin = carve(n * 4), o_plen = carve(n * 4), o_ifx = carve(n * 4),
+                 o_fof = carve(n * 4), o_res = carve(n * 4), o_ver = carve(n), o_tiles = carve((size_t)n_tiles * 8),
+                 o_nf = carve(4), o_map = carve((size_t)n_chunks * 4),
+                 o_tab = carve((size_t)n_ents * sizeof(infw_xdp_ring_ent));
+    uint8_t *sc = nullptr;
+    if (!a->pool || hipMallocFromPoolAsync(reinterpret_cast<void **>(&sc), bytes, a->pool, a->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return -ENOMEM;
+    }
+    const ChainFrames cf{reinterpret_cast<uint64_t *>(sc + o_off), reinterpret_cast<uint32_t *>(sc + o_lin),
+                         reinterpret_cast<uint32_t *>(sc + o_plen), reinterpret_cast<uint32_t *>(sc + o_ifx),
+                         reinterpret_cast<uint32_t *>(sc + o_fof), nullptr, nullptr, nullptr};
+    uint32_t *fres = reinterpret_cast<uint32_t *>(sc + o_res);
+    uint8_t *fver = sc + o_ver;
+    uint2 *tiles = reinterpret_cast<uint2 *>(sc + o_tiles);
+    uint32_t *n_frames = reinterpret_cast<uint32_t *>(sc + o_nf);
+    uint32_t *chunk_ring = reinterpret_cast<uint32_t *>(sc + o_map);
+    infw_xdp_ring_ent *table = reinterpret_cast<infw_xdp_ring_ent *>(sc + o_tab);
+    const uint8_t *umem0 = ents[0].umem;
+
+    RingGroup grp{};
+    for (uint32_t base = 0; base < n_ents; base += kRingGroup) {
+        const uint32_t cnt = n_ents - base < (uint32_t)kRingGroup ? n_ents - base : (uint32_t)kRingGroup;
+        for (uint32_t k = 0; k < cnt; k++) grp.e[k] = ents[base + k];
+        hipLaunchKernelGGL(xdp_rings_upload, dim3(1), dim3(kRingGroup), 0, a->stream, grp, cnt, table + base);
+    }
+    hipLaunchKernelGGL(xdp_rings_map, dim3((n_chunks + 255) / 256), dim3(256), 0, a->stream,
+                       (const infw_xdp_ring_ent *)table, n_ents, n_chunks, chunk_ring);
+    hipLaunchKernelGGL(xdp_rings_reduce, dim3(n_tiles), dim3(64 * kRingWaves), 0, a->stream,
+                       (const infw_xdp_ring_ent *)table, (const uint32_t *)chunk_ring, n_chunks, tiles);
+    hipLaunchKernelGGL(xdp_chain_carry, dim3(1), dim3(kCarry), 0, a->stream, tiles, n_tiles, n_frames);
+    hipLaunchKernelGGL(xdp_rings_emit, dim3(n_tiles), dim3(64 * kRingWaves), 0, a->stream,
+                       (const infw_xdp_ring_ent *)table, (const uint32_t *)chunk_ring, n_chunks, (const uint2 *)tiles,
+                       (const uint32_t *)n_frames, umem0, cf);
+    int rc = hipGetLastError() == hipSuccess ? 0 : -EIO;
+    if (rc == 0) {
+        const infw_frame_batch fb{umem0, cf.offsets, 0, cf.linear_len, cf.pkt_len, cf.ifindex};
+        infw_launch_args f = *a;
+        f.input = INFW_INPUT_FRAMES;
+        f.frames = &fb;
+        f.umem = nullptr;
+        f.xdp = nullptr;
+        f.results = any_res ? fres : nullptr;
+        f.verdicts = any_ver ? fver : nullptr;
+        f.ev = nullptr, f.ev_cap = 0, f.ev_count = nullptr;
+        rc = infw_launch_classify(&f);
+    }
+    if (rc == 0 && (any_res || any_ver)) {
+        const uint32_t cap = a->cus * 8;
+        hipLaunchKernelGGL(xdp_rings_scatter, dim3(n_tiles < cap ? n_tiles : cap), dim3(64 * kRingWaves), 0, a->stream,
+                           (const infw_xdp_ring_ent *)table, (const uint32_t *)chunk_ring, n_chunks,
+                           (const uint32_t *)cf.frame_of, (const uint32_t *)fres, (const uint8_t *)fver);
         if (hipGetLastError() != hipSuccess) rc = -EIO;
     }
     (void)hipFreeAsync(sc, a->stream);

@@ -96,7 +96,7 @@ class XdpDesc(C.Structure):
 
 
 class XdpRing(C.Structure):
-    """struct infw_xdp_ring (include/infw.h): one AF_XDP RX ring over a host umem (infw_classify_xdp_host)."""
+    """struct infw_xdp_ring (include/infw.h): one AF_XDP RX ring (infw_classify_xdp_host, infw_classify_xdp_rings)."""
     _fields_ = [("umem", C.c_void_p), ("descs", C.c_void_p), ("n", C.c_uint64), ("ifindex", C.c_uint32),
                 ("flags", C.c_uint32), ("results", C.c_void_p), ("verdicts", C.c_void_p)]
 
@@ -161,7 +161,7 @@ ABI_SYMBOLS = [
     "infw_get_launch", "infw_events_capture", "infw_build_id", "infw_table_export", "infw_table_import",
     "infw_table_delete_batch", "infw_set_option", "infw_get_option", "infw_option_name", "infw_classify_variant",
     "infw_kernel_variant_name", "infw_classify_xdp", "infw_classify_xdp_mb", "infw_classify_xdp_mb_ex",
-    "infw_events_capture_xdp", "infw_classify_xdp_host",
+    "infw_events_capture_xdp", "infw_classify_xdp_host", "infw_classify_xdp_rings",
     "infw_pack_xdp_host", "infw_launch_counts", "infw_xdp_host_events", "infw_classify_bursts_host",
     "infw_pack_burst_host", "infw_burst_host_events",
 ]
@@ -171,6 +171,7 @@ VARIANT_EVENTS = 0x1  # INFW_VARIANT_EVENTS
 XDP_PKT_CONTD = 1  # INFW_XDP_PKT_CONTD (linux/if_xdp.h): the frame continues in the next descriptor
 # csrc/infw_launch.h: descriptors per workgroup of infw_classify_xdp_mb's chain pass, tile summaries per carry round
 XDP_CHAIN_TILE, XDP_CHAIN_CARRY = 256, 512
+XDP_RINGS_MAX = 1024  # INFW_XDP_RINGS_MAX: rings per infw_classify_xdp_rings call
 
 
 # torch (device memory, streams, RCCL) ships its own libamdhip64.so.7; loading it
@@ -265,6 +266,7 @@ _sig = {
                                           C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infw_classify_xdp_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64]),
     "infw_pack_xdp_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, P(BatchSoaC)]),
+    "infw_classify_xdp_rings": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), C.c_uint32, C.c_void_p]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)

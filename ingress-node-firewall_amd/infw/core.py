@@ -398,6 +398,24 @@ class Classifier:
             arr[i] = N.XdpRing(ptr(umem), ptr(descs), n, ifindex, 0, ptr(results), ptr(verdicts))
         check(N.lib.infw_classify_xdp_host(self._ctx, dev, arr, len(rings), chunk), "classify_xdp_host")
 
+    def classify_xdp_rings(self, rings, dev: int = 0, stream=None) -> None:
+        """infw_classify_xdp_rings: every multi-buffer ring of a poll in one asynchronous call — what classify_xdp_mb
+        computes ring by ring, with one scratch allocation and one set of launches.  `rings`: (umem, descs, n,
+        ifindex, results, verdicts) per ring, the tuple classify_xdp_host takes, as torch tensors in HBM or pinned
+        host memory (or raw addresses); results / verdicts may be None per ring.  No chain runs from one ring into
+        the next; no event stream."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(torch.device("cuda", dev))
+        sp = stream if isinstance(stream, int) else stream.cuda_stream
+
+        def ptr(x):
+            return x if x is None or isinstance(x, int) else x.data_ptr()
+        arr = (N.XdpRing * max(1, len(rings)))()
+        for i, (umem, descs, n, ifindex, results, verdicts) in enumerate(rings):
+            arr[i] = N.XdpRing(ptr(umem), ptr(descs), n, ifindex, 0, ptr(results), ptr(verdicts))
+        check(N.lib.infw_classify_xdp_rings(self._ctx, dev, arr, len(rings), sp), "classify_xdp_rings")
+
     def classify_bursts_host(self, bursts, chunk: int = 0, dev: int = 0) -> None:
         """infw_classify_bursts_host (include/infw_host.h): DPDK-style bursts of frames in host memory — per burst a
         `Burst` (frame pointers, linear and frame lengths, ifindex, optional result / verdict arrays) — packed on the

@@ -6,13 +6,19 @@ checked), then the same descriptors as chains of 3 (a third of the lookups).  Pr
 --events: the same two rings also with a deny-event buffer of n records (infw_classify_xdp_mb_ex), alternated with the
 plain calls, and infw_events_capture_xdp timed over the records the chains of 3 produced.
 
-    python tools/xdp_mb_bench.py [--n 16777216] [--rounds 20] [--events]
+--rings [R] --ring-n M: the shape a daemon polls — R rings (default 64) of M descriptors (default 2048), chains of 1-3,
+each ring its own umem in HBM and the interfaces of the workload in turn — (a) as R calls of infw_classify_xdp_mb and
+(b) as one infw_classify_xdp_rings, alternated over the same data (the answers are compared once); then one ring of
+--n descriptors through both calls.  Per arm: HIP events around the group and the host's wall-clock time of issuing it.
+
+    python tools/xdp_mb_bench.py [--n 16777216] [--rounds 20] [--events] [--rings [64] --ring-n 2048]
 """
 import ctypes as C
 import argparse
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ingress-node-firewall_amd"))
@@ -26,11 +32,68 @@ from infw import workloads as W  # noqa: E402
 STRIDE = 2048
 
 
+def rings_mode(args, clf, wl):
+    n, R, M, dev = args.n, args.rings, args.ring_n, torch.device("cuda", 0)
+    assert R * M <= n and args.rounds >= 20, "the rings are cut from the large ring's umem; at least 20 timed rounds"
+    umem = torch.zeros(n * STRIDE, dtype=torch.uint8, device=dev)
+    lin, plen, ifx = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    wl.gen_frames_device(umem, STRIDE, lin, plen, ifx, 0, 0)
+    ifs = torch.argsort(torch.bincount(ifx), descending=True).tolist()
+    ifs = ifs[:int((torch.bincount(ifx) > 0).sum())]
+    rng = np.random.default_rng(3)
+    opt = np.full(n, infw.XDP_PKT_CONTD, np.int32)  # chain lengths drawn from {1, 2, 3}
+    opt[np.cumsum(rng.integers(1, 4, n))[:n].clip(max=n) - 1] = 0
+    desc = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    addr = torch.arange(n, dtype=torch.int64, device=dev) * STRIDE
+    desc[:, 0], desc[:, 1] = (addr & 0xFFFFFFFF).to(torch.int32), (addr >> 32).to(torch.int32)
+    desc[:, 2], desc[:, 3] = torch.where(lin < 80, lin, plen), torch.from_numpy(opt).to(dev)
+    small = desc[:R * M].clone()  # ring r: descriptors [r M, (r + 1) M) over its own umem, addresses from 0
+    small[:, 0], small[:, 1] = desc[:M, 0].repeat(R), desc[:M, 1].repeat(R)
+    res, res2 = (torch.full((n,), -1, dtype=torch.int32, device=dev) for _ in range(2))
+    ver = torch.empty(n, dtype=torch.uint8, device=dev)
+
+    def rings(out):
+        return [(umem[r * M * STRIDE:(r + 1) * M * STRIDE], small[r * M:(r + 1) * M], M, ifs[r % len(ifs)],
+                 out[r * M:(r + 1) * M], ver[r * M:(r + 1) * M]) for r in range(R)]
+    ra, rb = rings(res), rings(res2)
+    arms = {"per_ring_calls": lambda: [clf.classify_xdp_mb(u, d, m, i, results=o, verdicts=v) for u, d, m, i, o, v in ra],
+            "one_rings_call": lambda: clf.classify_xdp_rings(rb),
+            "large_xdp_mb": lambda: clf.classify_xdp_mb(umem, desc, n, ifs[0], results=res, verdicts=ver),
+            "large_xdp_rings": lambda: clf.classify_xdp_rings([(umem, desc, n, ifs[0], res2, ver)])}
+    dev_ms, host_ms = {k: [] for k in arms}, {k: [] for k in arms}
+    for rnd in range(-3, args.rounds):  # three warm-up rounds
+        for k, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            fn()
+            e1.record()
+            t1 = time.perf_counter()
+            e1.synchronize()
+            if rnd >= 0:
+                dev_ms[k].append(e0.elapsed_time(e1))
+                host_ms[k].append((t1 - t0) * 1e3)
+            if rnd == -3 and k in ("one_rings_call", "large_xdp_rings"):
+                assert torch.equal(res, res2), k + ": differs from infw_classify_xdp_mb ring by ring"
+                res.fill_(-1), res2.fill_(-1)
+    stat = lambda t: {k: {"median": float(np.median(v)), "min": min(v), "max": max(v)} for k, v in t.items()}
+    d, h = stat(dev_ms), stat(host_ms)
+    print(json.dumps({"rings": R, "ring_n": M, "n_large": n, "rounds": args.rounds,
+                      "kernel": clf.variant(infw.INPUT_FRAMES), "event_ms": d, "host_issue_ms": h,
+                      "per_ring_over_one_call_event": d["per_ring_calls"]["median"] / d["one_rings_call"]["median"],
+                      "per_ring_over_one_call_host": h["per_ring_calls"]["median"] / h["one_rings_call"]["median"],
+                      "large_mb_over_large_rings_event": d["large_xdp_mb"]["median"] / d["large_xdp_rings"]["median"],
+                      "gdesc_per_s": {k: (n if k.startswith("large") else R * M) / v["median"] / 1e6
+                                      for k, v in d.items()}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 24)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--events", action="store_true")
+    ap.add_argument("--rings", type=int, nargs="?", const=64, default=0)
+    ap.add_argument("--ring-n", type=int, default=2048)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     n, dev = args.n, torch.device("cuda", 0)
@@ -38,6 +101,8 @@ def main():
     clf = infw.Classifier(devices=[0], max_entries=wl.n_entries + 16)
     wl.load_into(clf)
     clf.commit()
+    if args.rings:
+        return rings_mode(args, clf, wl)
     umem = torch.zeros(n * STRIDE, dtype=torch.uint8, device=dev)
     lin, plen, ifx = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
     wl.gen_frames_device(umem, STRIDE, lin, plen, ifx, 0, 0)
