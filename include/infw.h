@@ -463,8 +463,8 @@ int infw_classify_xdp_host(infw_ctx *ctx, int dev, const struct infw_xdp_ring *r
 /* ring; a ring of n has ceil(n / 64)), 8 B per 4 chunks, 48 B per non-empty   */
 /* ring and 4 B, each array rounded up to 16 B.  -ENODEV: host-only context.   */
 /* Nothing is launched when an error is returned; n_rings == 0 returns 0.      */
-/* No deny events: a caller that needs them calls infw_classify_xdp_mb_ex per  */
-/* ring.                                                                       */
+/* Deny events and their perf samples: infw_classify_xdp_rings_ex and           */
+/* infw_events_capture_xdp_rings (declared with the sidebands below).          */
 #define INFW_XDP_RINGS_MAX 1024
 int infw_classify_xdp_rings(infw_ctx *ctx, int dev, const struct infw_xdp_ring *rings, uint32_t n_rings,
                             void *stream);
@@ -574,6 +574,54 @@ int infw_events_capture(infw_ctx *ctx, int dev, const struct infw_frame_batch *f
 int infw_events_capture_xdp(infw_ctx *ctx, int dev, const uint8_t *umem, const struct infw_xdp_desc *descs,
                             uint64_t n, const struct infw_event_rec *events, uint64_t events_cap,
                             const uint64_t *events_count, struct infw_event_sample *samples, void *stream);
+
+/* infw_classify_xdp_rings with the deny-event stream.  ex == NULL or           */
+/* ex->events == NULL is infw_classify_xdp_rings itself (same result words,    */
+/* verdicts and counters either way).  With ex->events it appends one record   */
+/* per frame (descriptor chain) a rule denies, with infw_classify_xdp_mb_ex's  */
+/* discipline (one atomic per wave, order across waves unspecified,            */
+/* *events_count counts past events_cap; records already in the buffer are not */
+/* touched): hdr.ifId = (u16) the ring's own ifindex, hdr.pktLength = (u16)    */
+/* the chain's summed len, captured = min(sum, 256), and pkt_index = the FLAT  */
+/* index of the frame's head descriptor: the sum of rings[q].n over q < r,     */
+/* plus i, for descriptor i of rings[r] (empty rings add nothing; the caller   */
+/* gets ring and i back with its own prefix sums).                             */
+/* With ex->samples too (the fused capture) the call also writes samples[k]    */
+/* for the records it appended — slots [count before, min(count after,         */
+/* events_cap)) — from the ring table it already has on the device; slots of   */
+/* earlier records are left as they are.  samples: device memory of events_cap */
+/* slots, 8-byte aligned.  Sample bytes as infw_events_capture_xdp defines     */
+/* them, the chain bounded by its OWN ring: it ends at the first descriptor    */
+/* with PKT_CONTD clear or at the ring's last descriptor; no descriptor of     */
+/* another ring is read, and no byte outside [buffer_j, buffer_j + len_j) of a */
+/* chain member.                                                               */
+/* Errnos as infw_classify_xdp_rings, plus -EINVAL for size <                  */
+/* sizeof(struct infw_xdp_rings_ex), flags != 0, events without events_count,  */
+/* samples without events, samples not 8-byte aligned.  -ENOMEM: the scratch   */
+/* of infw_classify_xdp_rings plus, with events, 4 B per descriptor and 8 B.   */
+/* Nothing is launched when an error is returned.                              */
+struct infw_xdp_rings_ex {
+    uint32_t size;                      /* sizeof(struct infw_xdp_rings_ex) */
+    uint32_t flags;                     /* 0 */
+    struct infw_event_rec *events;      /* device buffer, or NULL: no event stream */
+    uint64_t events_cap;
+    uint64_t *events_count;             /* device u64 */
+    struct infw_event_sample *samples;  /* device, events_cap slots, 8-B aligned, or NULL */
+};
+int infw_classify_xdp_rings_ex(infw_ctx *ctx, int dev, const struct infw_xdp_ring *rings, uint32_t n_rings,
+                               const struct infw_xdp_rings_ex *ex, void *stream);
+/* The stand-alone capture, for a caller that sizes `samples` after reading    */
+/* the count: the same `rings` array in the same order, samples[k] for every   */
+/* k < min(*events_count, events_cap).  Stream-ordered after the classify (the */
+/* count is read on the device).  A record with pkt_index >= the sum of the    */
+/* rings' n (a record of another batch) gets its size and header and no frame  */
+/* bytes.  Rings validated as by infw_classify_xdp_rings (results / verdicts   */
+/* are not used); -EINVAL also for events_cap != 0 with a NULL events,         */
+/* events_count or samples, or samples not 8-byte aligned; -ENOMEM: no scratch */
+/* for the ring table (48 B per non-empty ring from the context's pool).       */
+int infw_events_capture_xdp_rings(infw_ctx *ctx, int dev, const struct infw_xdp_ring *rings, uint32_t n_rings,
+                                  const struct infw_event_rec *events, uint64_t events_cap,
+                                  const uint64_t *events_count, struct infw_event_sample *samples, void *stream);
 
 /* Host-resident batch: the SoA streams, result words and verdicts live in   */
 /* host memory (as a cgo caller hands them over).  The batch goes through    */

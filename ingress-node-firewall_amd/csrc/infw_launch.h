@@ -73,9 +73,18 @@ int infw_launch_classify_xdp_mb(const infw_launch_args *a);
 // infw_classify_xdp_rings (xdpchain.hip): the same for `n_ents` non-empty rings at once — one allocation, one set of
 // launches, one free; no chain runs from one ring into the next.  ents[r].chunk0 / flat0 are the running sums of
 // ceil(n / 64) and n; a->n is the sum of n (< 2^31), n_chunks the sum of the chunks; a->results / verdicts / umem /
-// xdp are ignored (each ring has its own).  `ents` is read before the call returns.  No event stream.  0, -EIO, -ENOMEM.
+// xdp are ignored (each ring has its own).  `ents` is read before the call returns.  0, -EIO, -ENOMEM.
+// With a->ev_count (infw_classify_xdp_rings_ex) the records this call appended get pkt_index = the flat index of the
+// frame's head (ents[r].flat0 + i) and ifId from the ring's own ifindex; with `samples` too, their perf samples are
+// written from the table already in scratch (slots [count before, min(count after, a->ev_cap)), no others).
 int infw_launch_classify_xdp_rings(const infw_launch_args *a, const infw_xdp_ring_ent *ents, uint32_t n_ents,
-                                   uint32_t n_chunks);
+                                   uint32_t n_chunks, infw_event_sample *samples);
+// infw_events_capture_xdp_rings (xdpchain.hip): samples[k] for k < min(*count, cap) over the same `ents` (total = the
+// sum of their n): a record's ring is found from its flat pkt_index, its chain walked inside that ring.  One
+// allocation from `pool` (48 B per entry).  Asynchronous.  0, -EIO, -ENOMEM.
+int infw_launch_event_samples_xdp_rings(const infw_xdp_ring_ent *ents, uint32_t n_ents, uint64_t total,
+                                        const infw_event_rec *ev, uint64_t cap, const uint64_t *count,
+                                        infw_event_sample *samples, uint32_t cus, hipMemPool_t pool, hipStream_t stream);
 // infw_events_capture_xdp (xdpchain.hip): samples[k] for k < min(*count, cap), each record's first `captured` frame
 // bytes gathered across the descriptor chain that starts at its pkt_index.  Asynchronous.  0, -EIO.
 int infw_launch_event_samples_xdp(const uint8_t *umem, const infw_xdp_desc *descs, uint64_t n,

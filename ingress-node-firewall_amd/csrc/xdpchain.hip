@@ -29,7 +29,9 @@
 //                      gathered across the chain's buffers — the one place a continuation's addr is dereferenced
 //
 // Many rings in one call (infw_classify_xdp_rings): the same passes over 64-descriptor chunks of all the rings, with a
-// ring table and a chunk -> ring map in scratch — the xdp_rings_* kernels below.
+// ring table and a chunk -> ring map in scratch — the xdp_rings_* kernels below.  Their deny events
+// (infw_classify_xdp_rings_ex) carry the flat index of the frame's head; xdp_rings_event_samples finds each record's
+// ring in the table's flat-index column (staged in LDS, two wave-wide compares) and walks the chain inside that ring.
 #include <hip/hip_runtime.h>
 #include <errno.h>
 #include <stdint.h>
@@ -254,68 +256,75 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {  // unsegmented
     return x;
 }
 
+// One record, by one wave: the slot of record `e`, whose chain starts at descriptor h of the ring (umem, descs, n) —
+// or, with in_ring false, belongs to no ring of the call — built in the wave's image and stored to `slot`.
+__device__ __forceinline__ void sample_record(uint64_t *__restrict__ img8, const infw_event_rec &e,
+                                              const uint8_t *__restrict__ umem,
+                                              const infw_xdp_desc *__restrict__ descs, uint64_t n, uint64_t h,
+                                              bool in_ring, uint8_t *__restrict__ slot) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint8_t *const img = reinterpret_cast<uint8_t *>(img8);
+    const uint32_t captured = e.captured < INFW_MAX_EVENT_DATA ? e.captured : INFW_MAX_EVENT_DATA;
+    if (lane < kSampleWords) img8[lane] = 0;
+    wave_lds_handoff();
+    uint32_t covered = 0;  // frame bytes the descriptors of earlier rounds hold (clamped: >= captured ends the walk)
+    bool open = in_ring;   // a record of another batch: size and header only
+    for (uint64_t at = h; open && covered < captured; at += 64) {
+        const uint64_t i = at + lane;
+        uint64_t addr = 0;
+        uint32_t len = 0, opt = 0;
+        if (i < n) {
+            const u32x4 d = *(reinterpret_cast<const u32x4 *>(descs) + i);
+            addr = (uint64_t)d[1] << 32 | d[0];
+            len = d[2];
+            opt = d[3];
+        }
+        // lanes at or past n close the chain too, so nothing behind the ring's end is summed (i == n - 1 is first)
+        const uint64_t ends = __ballot(i + 1 >= n || !(opt & INFW_XDP_PKT_CONTD));
+        const uint32_t last = ends ? (uint32_t)__builtin_ctzll(ends) : 63u;
+        open = ends == 0;
+        const uint32_t l = lane <= last ? (len < INFW_MAX_EVENT_DATA ? len : INFW_MAX_EVENT_DATA) : 0u;
+        const uint32_t incl = wave_scan_incl(l);
+        const uint32_t S = covered + incl - l;
+        uint64_t live = __ballot(l != 0 && S < captured);
+        const uint64_t src = (addr & ((1ull << 48) - 1)) + (addr >> 48);
+        while (live) {  // wave-uniform
+            const int j = __builtin_ctzll(live);
+            live &= live - 1;
+            const uint64_t sj = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(src >> 32), j) << 32 |
+                                (uint32_t)__builtin_amdgcn_readlane((int)src, j);
+            const uint32_t Sj = (uint32_t)__builtin_amdgcn_readlane((int)S, j);
+            const uint32_t lj = (uint32_t)__builtin_amdgcn_readlane((int)l, j);
+            const uint32_t room = captured - Sj, cnt = lj < room ? lj : room;  // Sj < captured <= 256
+            const uint8_t *__restrict__ f = umem + sj;
+            for (uint32_t b = lane; b < cnt; b += 64) img[12u + Sj + b] = f[b];
+        }
+        covered += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+    if (lane == 0) {
+        uint32_t hw[2];
+        __builtin_memcpy(hw, &e.hdr, 8);
+        uint32_t *const img4 = reinterpret_cast<uint32_t *>(img);
+        img4[0] = ((8u + e.captured + 4u + 7u) & ~7u) - 4u;  // perf's raw size, as event_samples_kernel writes it
+        img4[1] = hw[0];
+        img4[2] = hw[1];
+    }
+    wave_lds_handoff();
+    if (lane < kSampleWords) reinterpret_cast<uint64_t *>(slot)[lane] = img8[lane];
+    wave_lds_handoff();  // the next record rewrites the image
+}
+
 __global__ __launch_bounds__(64 * kSampleWaves) void xdp_event_samples_kernel(
     const uint8_t *__restrict__ umem, const infw_xdp_desc *__restrict__ descs, uint64_t n,
     const infw_event_rec *__restrict__ ev, uint64_t cap, const uint64_t *__restrict__ count,
     uint8_t *__restrict__ out) {
     __shared__ uint64_t s_img[kSampleWaves][kSampleWords];
     const uint64_t c = *count, n_rec = c < cap ? c : cap;
-    const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // the record is wave-uniform
-    uint64_t *const img8 = s_img[wv];
-    uint8_t *const img = reinterpret_cast<uint8_t *>(img8);
     const uint64_t waves = (uint64_t)gridDim.x * kSampleWaves;
     for (uint64_t r = (uint64_t)blockIdx.x * kSampleWaves + wv; r < n_rec; r += waves) {
         const infw_event_rec e = ev[r];
-        const uint64_t h = e.pkt_index;
-        const uint32_t captured = e.captured < INFW_MAX_EVENT_DATA ? e.captured : INFW_MAX_EVENT_DATA;
-        if (lane < kSampleWords) img8[lane] = 0;
-        wave_lds_handoff();
-        uint32_t covered = 0;  // frame bytes the descriptors of earlier rounds hold (clamped: >= captured ends the walk)
-        bool open = h < n;     // a record of another batch: size and header only
-        for (uint64_t at = h; open && covered < captured; at += 64) {
-            const uint64_t i = at + lane;
-            uint64_t addr = 0;
-            uint32_t len = 0, opt = 0;
-            if (i < n) {
-                const u32x4 d = *(reinterpret_cast<const u32x4 *>(descs) + i);
-                addr = (uint64_t)d[1] << 32 | d[0];
-                len = d[2];
-                opt = d[3];
-            }
-            // lanes at or past n close the chain too, so nothing behind the ring's end is summed (i == n - 1 is first)
-            const uint64_t ends = __ballot(i + 1 >= n || !(opt & INFW_XDP_PKT_CONTD));
-            const uint32_t last = ends ? (uint32_t)__builtin_ctzll(ends) : 63u;
-            open = ends == 0;
-            const uint32_t l = lane <= last ? (len < INFW_MAX_EVENT_DATA ? len : INFW_MAX_EVENT_DATA) : 0u;
-            const uint32_t incl = wave_scan_incl(l);
-            const uint32_t S = covered + incl - l;
-            uint64_t live = __ballot(l != 0 && S < captured);
-            const uint64_t src = (addr & ((1ull << 48) - 1)) + (addr >> 48);
-            while (live) {  // wave-uniform
-                const int j = __builtin_ctzll(live);
-                live &= live - 1;
-                const uint64_t sj = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(src >> 32), j) << 32 |
-                                    (uint32_t)__builtin_amdgcn_readlane((int)src, j);
-                const uint32_t Sj = (uint32_t)__builtin_amdgcn_readlane((int)S, j);
-                const uint32_t lj = (uint32_t)__builtin_amdgcn_readlane((int)l, j);
-                const uint32_t room = captured - Sj, cnt = lj < room ? lj : room;  // Sj < captured <= 256
-                const uint8_t *__restrict__ f = umem + sj;
-                for (uint32_t b = lane; b < cnt; b += 64) img[12u + Sj + b] = f[b];
-            }
-            covered += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-        if (lane == 0) {
-            uint32_t hw[2];
-            __builtin_memcpy(hw, &e.hdr, 8);
-            uint32_t *const img4 = reinterpret_cast<uint32_t *>(img);
-            img4[0] = ((8u + e.captured + 4u + 7u) & ~7u) - 4u;  // perf's raw size, as event_samples_kernel writes it
-            img4[1] = hw[0];
-            img4[2] = hw[1];
-        }
-        wave_lds_handoff();
-        if (lane < kSampleWords) reinterpret_cast<uint64_t *>(out + r * INFW_EVENT_SAMPLE_BYTES)[lane] = img8[lane];
-        wave_lds_handoff();  // the next record rewrites the image
+        sample_record(s_img[wv], e, umem, descs, n, e.pkt_index, e.pkt_index < n, out + r * INFW_EVENT_SAMPLE_BYTES);
     }
 }
 
@@ -413,6 +422,7 @@ __global__ __launch_bounds__(64 * kRingWaves) void xdp_rings_emit(const infw_xdp
     // s.heads >= 1 on every lane, so the length carried in from the ring before (pre.y) is never added
     const uint32_t frame = pre.x + s.heads - 1u;
     const uint64_t g = e.flat0 + i;
+    if (g == 0 && out.ev_before) *out.ev_before = *out.ev_count;
     out.frame_of[g] = frame;
     if (g >= *n_frames) {  // a slot no frame owns (frame < n_frames <= g: no head or closer writes it)
         out.offsets[g] = 0;
@@ -424,6 +434,7 @@ __global__ __launch_bounds__(64 * kRingWaves) void xdp_rings_emit(const infw_xdp
         out.offsets[frame] = (uint64_t)(e.umem - umem0) + (s.addr & ((1ull << 48) - 1)) + (s.addr >> 48);
         out.linear_len[frame] = s.len;
         out.ifindex[frame] = e.ifindex;
+        if (out.head_of) out.head_of[frame] = (uint32_t)g;
     }
     if (!(s.opt & INFW_XDP_PKT_CONTD) || i == e.n - 1u) out.pkt_len[frame] = s.sum + (s.heads ? 0u : pre.y);
 }
@@ -443,6 +454,51 @@ __global__ __launch_bounds__(64 * kRingWaves) void xdp_rings_scatter(const infw_
         const uint32_t f = __builtin_nontemporal_load(&frame_of[e.flat0 + i]);
         if (e.results) __builtin_nontemporal_store(fres[f], &e.results[i]);
         if (e.verdicts) __builtin_nontemporal_store(fver[f], &e.verdicts[i]);
+    }
+}
+
+// ---- infw_classify_xdp_rings_ex / infw_events_capture_xdp_rings: perf samples over the rings of one call ----------
+//
+// A record's pkt_index is the flat index of its frame's head (the ring's first flat index + i), so the sample kernel
+// has one thing to do before the walk of xdp_event_samples_kernel: find the record's ring.  The table's first-flat-index
+// column is strictly increasing (its rings are non-empty) and at most INFW_XDP_RINGS_MAX long:
+//   stage   every workgroup copies the column into LDS once (4 KiB, entries past the table = 2^32 - 1, above every
+//           flat index), one barrier, before the record loop
+//   locate  per record, by its wave: lane l compares entry 16 l with pkt_index, the ballot is a run of ones from
+//           lane 0 (entry 0 is 0) whose popcount names the block of 16; lanes 0..15 compare the block's entries, the
+//           second ballot's popcount names the ring — two LDS reads, no dependent chain of global loads
+//   walk    the ring's 48-B entry is loaded wave-uniformly; the chain starts at h = pkt_index - flat0 of the ring's own
+//           descs and is bounded by the ring's own n, so it ends at the ring's last descriptor whatever follows it in
+//           memory; the fragments are read from the ring's own umem (sample_record)
+// Persistent grid-stride grid, one wave per record, no workgroup barrier inside the loop.  `first` (the fused form:
+// the count's snapshot xdp_rings_emit took) names the first record to sample; null is 0.
+constexpr uint32_t kRingsMax = INFW_XDP_RINGS_MAX;
+static_assert(kRingsMax == 64 * 16, "two levels of the wave-wide search: 64 blocks of 16 entries");
+
+__global__ __launch_bounds__(64 * kSampleWaves) void xdp_rings_event_samples(
+    const infw_xdp_ring_ent *__restrict__ table, uint32_t n_ents, uint64_t total,
+    const infw_event_rec *__restrict__ ev, uint64_t cap, const uint64_t *__restrict__ first,
+    const uint64_t *__restrict__ count, uint8_t *__restrict__ out) {
+    __shared__ uint32_t s_flat0[kRingsMax];
+    __shared__ uint64_t s_img[kSampleWaves][kSampleWords];
+    for (uint32_t t = threadIdx.x; t < kRingsMax; t += 64 * kSampleWaves) s_flat0[t] = t < n_ents ? table[t].flat0 : ~0u;
+    __syncthreads();
+    const uint64_t c = *count, n_rec = c < cap ? c : cap;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // the record is wave-uniform
+    const uint64_t waves = (uint64_t)gridDim.x * kSampleWaves;
+    for (uint64_t r = (first ? *first : 0) + (uint64_t)blockIdx.x * kSampleWaves + wv; r < n_rec; r += waves) {
+        const infw_event_rec e = ev[r];
+        const bool in_ring = e.pkt_index < total;  // total < 2^31; else a record of another batch: size and header only
+        infw_xdp_ring_ent g{};
+        if (in_ring) {  // wave-uniform
+            const uint32_t p = (uint32_t)e.pkt_index;
+            const uint32_t blk = (uint32_t)__popcll(__ballot(s_flat0[16u * lane] <= p)) - 1u;  // lane 0 always votes
+            const uint32_t at = (uint32_t)__popcll(__ballot(lane < 16u && s_flat0[16u * blk + (lane & 15u)] <= p)) - 1u;
+            g = table[__builtin_amdgcn_readfirstlane((int)(16u * blk + at))];  // < n_ents: the padding is above p
+        }
+        sample_record(s_img[wv], e, g.umem, g.descs, g.n, e.pkt_index - g.flat0, in_ring,
+                      out + r * INFW_EVENT_SAMPLE_BYTES);
     }
 }
 
@@ -515,17 +571,39 @@ extern "C" int infw_launch_classify_xdp_mb(const infw_launch_args *a) {
     return rc;
 }
 
+// The ring table into scratch, stream-ordered: INFW_XDP_RINGS_GROUP entries per launch, by value.
+static void upload_ring_table(const infw_xdp_ring_ent *ents, uint32_t n_ents, infw_xdp_ring_ent *table,
+                              hipStream_t stream) {
+    RingGroup grp{};
+    for (uint32_t base = 0; base < n_ents; base += kRingGroup) {
+        const uint32_t cnt = n_ents - base < (uint32_t)kRingGroup ? n_ents - base : (uint32_t)kRingGroup;
+        for (uint32_t k = 0; k < cnt; k++) grp.e[k] = ents[base + k];
+        hipLaunchKernelGGL(xdp_rings_upload, dim3(1), dim3(kRingGroup), 0, stream, grp, cnt, table + base);
+    }
+}
+
+// One wave per record, kSampleWaves per workgroup, at most `most` records to sample, the grid capped per CU.
+static void launch_rings_samples(const infw_xdp_ring_ent *table, uint32_t n_ents, uint64_t total,
+                                 const infw_event_rec *ev, uint64_t cap, const uint64_t *first, const uint64_t *count,
+                                 infw_event_sample *samples, uint64_t most, uint32_t cus, hipStream_t stream) {
+    const uint64_t blocks = (most + kSampleWaves - 1) / kSampleWaves, lim = 8ull * cus;
+    hipLaunchKernelGGL(xdp_rings_event_samples, dim3((uint32_t)(blocks < lim ? blocks : lim)), dim3(64 * kSampleWaves),
+                       0, stream, table, n_ents, total, ev, cap, first, count, reinterpret_cast<uint8_t *>(samples));
+}
+
 // ents: the call's non-empty rings with their first chunk and first flat index filled in (abi.cpp), read before the
 // call returns; a->n is the sum of their n (< 2^31), n_chunks the sum of their chunks.
 extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const infw_xdp_ring_ent *ents, uint32_t n_ents,
-                                              uint32_t n_chunks) {
+                                              uint32_t n_chunks, infw_event_sample *samples) {
     const uint64_t n = a->n;
     if (n == 0 || n_ents == 0) return 0;
     const uint32_t n_tiles = (n_chunks + kRingWaves - 1) / kRingWaves;
+    const bool events = a->ev_count != nullptr;
     bool any_res = false, any_ver = false;
     for (uint32_t r = 0; r < n_ents; r++) any_res |= ents[r].results != nullptr, any_ver |= ents[r].verdicts != nullptr;
     // one stream-ordered allocation, carved at 16-B boundaries: 29 B per descriptor as for one ring, 4 B per chunk
-    // (its ring), 8 B per workgroup of kRingWaves chunks (its summary), 48 B per ring (the table) and the frame count
+    // (its ring), 8 B per workgroup of kRingWaves chunks (its summary), 48 B per ring (the table) and the frame count;
+    // with the event stream 4 B more per descriptor (head_of) and the count's snapshot
     size_t bytes = 0;
     auto carve = [&](size_t sz) {
         const size_t at = bytes;
@@ -535,15 +613,18 @@ extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const i
     const size_t o_off = carve(n * 8), o_lin = carve(n * 4), o_plen = carve(n * 4), o_ifx = carve(n * 4),
                  o_fof = carve(n * 4), o_res = carve(n * 4), o_ver = carve(n), o_tiles = carve((size_t)n_tiles * 8),
                  o_nf = carve(4), o_map = carve((size_t)n_chunks * 4),
-                 o_tab = carve((size_t)n_ents * sizeof(infw_xdp_ring_ent));
+                 o_tab = carve((size_t)n_ents * sizeof(infw_xdp_ring_ent)), o_hof = carve(events ? n * 4 : 0),
+                 o_evb = carve(events ? 8 : 0);
     uint8_t *sc = nullptr;
     if (!a->pool || hipMallocFromPoolAsync(reinterpret_cast<void **>(&sc), bytes, a->pool, a->stream) != hipSuccess) {
         (void)hipGetLastError();
         return -ENOMEM;
     }
+    uint32_t *head_of = events ? reinterpret_cast<uint32_t *>(sc + o_hof) : nullptr;
+    uint64_t *ev_before = events ? reinterpret_cast<uint64_t *>(sc + o_evb) : nullptr;
     const ChainFrames cf{reinterpret_cast<uint64_t *>(sc + o_off), reinterpret_cast<uint32_t *>(sc + o_lin),
                          reinterpret_cast<uint32_t *>(sc + o_plen), reinterpret_cast<uint32_t *>(sc + o_ifx),
-                         reinterpret_cast<uint32_t *>(sc + o_fof), nullptr, nullptr, nullptr};
+                         reinterpret_cast<uint32_t *>(sc + o_fof), head_of, a->ev_count, ev_before};
     uint32_t *fres = reinterpret_cast<uint32_t *>(sc + o_res);
     uint8_t *fver = sc + o_ver;
     uint2 *tiles = reinterpret_cast<uint2 *>(sc + o_tiles);
@@ -552,12 +633,7 @@ extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const i
     infw_xdp_ring_ent *table = reinterpret_cast<infw_xdp_ring_ent *>(sc + o_tab);
     const uint8_t *umem0 = ents[0].umem;
 
-    RingGroup grp{};
-    for (uint32_t base = 0; base < n_ents; base += kRingGroup) {
-        const uint32_t cnt = n_ents - base < (uint32_t)kRingGroup ? n_ents - base : (uint32_t)kRingGroup;
-        for (uint32_t k = 0; k < cnt; k++) grp.e[k] = ents[base + k];
-        hipLaunchKernelGGL(xdp_rings_upload, dim3(1), dim3(kRingGroup), 0, a->stream, grp, cnt, table + base);
-    }
+    upload_ring_table(ents, n_ents, table, a->stream);
     hipLaunchKernelGGL(xdp_rings_map, dim3((n_chunks + 255) / 256), dim3(256), 0, a->stream,
                        (const infw_xdp_ring_ent *)table, n_ents, n_chunks, chunk_ring);
     hipLaunchKernelGGL(xdp_rings_reduce, dim3(n_tiles), dim3(64 * kRingWaves), 0, a->stream,
@@ -568,6 +644,8 @@ extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const i
                        (const uint32_t *)n_frames, umem0, cf);
     int rc = hipGetLastError() == hipSuccess ? 0 : -EIO;
     if (rc == 0) {
+        // a->ev / ev_cap / ev_count go with the copy: the frames kernel's event instantiation appends the records,
+        // ifId from the frame's own ifindex
         const infw_frame_batch fb{umem0, cf.offsets, 0, cf.linear_len, cf.pkt_len, cf.ifindex};
         infw_launch_args f = *a;
         f.input = INFW_INPUT_FRAMES;
@@ -576,8 +654,18 @@ extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const i
         f.xdp = nullptr;
         f.results = any_res ? fres : nullptr;
         f.verdicts = any_ver ? fver : nullptr;
-        f.ev = nullptr, f.ev_cap = 0, f.ev_count = nullptr;
         rc = infw_launch_classify(&f);
+    }
+    if (rc == 0 && events && a->ev_cap) {  // at most one new record per frame, and none past the capacity
+        const uint64_t most = n < a->ev_cap ? n : a->ev_cap, blocks = (most + 255) / 256, cap = (uint64_t)a->cus * 8;
+        hipLaunchKernelGGL(xdp_event_remap, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(256), 0, a->stream,
+                           a->ev, a->ev_cap, (const uint64_t *)ev_before, (const uint64_t *)a->ev_count,
+                           (const uint32_t *)head_of, n);
+        // the fused capture: the records this call appended, from the table already in scratch
+        if (samples)
+            launch_rings_samples(table, n_ents, n, a->ev, a->ev_cap, ev_before, a->ev_count, samples, most, a->cus,
+                                 a->stream);
+        if (hipGetLastError() != hipSuccess) rc = -EIO;
     }
     if (rc == 0 && (any_res || any_ver)) {
         const uint32_t cap = a->cus * 8;
@@ -587,6 +675,28 @@ extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const i
         if (hipGetLastError() != hipSuccess) rc = -EIO;
     }
     (void)hipFreeAsync(sc, a->stream);
+    return rc;
+}
+
+// The stand-alone capture: the table alone goes to scratch (48 B per non-empty ring), then the sample kernel over
+// every record below min(*count, cap).  With no non-empty ring every record is one of another batch.
+extern "C" int infw_launch_event_samples_xdp_rings(const infw_xdp_ring_ent *ents, uint32_t n_ents, uint64_t total,
+                                                   const infw_event_rec *ev, uint64_t cap, const uint64_t *count,
+                                                   infw_event_sample *samples, uint32_t cus, hipMemPool_t pool,
+                                                   hipStream_t stream) {
+    if (cap == 0) return 0;
+    infw_xdp_ring_ent *table = nullptr;
+    if (n_ents) {
+        if (!pool || hipMallocFromPoolAsync(reinterpret_cast<void **>(&table), (size_t)n_ents * sizeof(*table), pool,
+                                            stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return -ENOMEM;
+        }
+        upload_ring_table(ents, n_ents, table, stream);
+    }
+    launch_rings_samples(table, n_ents, total, ev, cap, nullptr, count, samples, cap, cus, stream);
+    const int rc = hipGetLastError() == hipSuccess ? 0 : -EIO;
+    if (table) (void)hipFreeAsync(table, stream);
     return rc;
 }
 

@@ -126,6 +126,12 @@ class ClassifyEx(C.Structure):
                 ("events_count", C.c_void_p)]
 
 
+class XdpRingsEx(C.Structure):
+    """struct infw_xdp_rings_ex (include/infw.h)."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("events", C.c_void_p), ("events_cap", C.c_uint64),
+                ("events_count", C.c_void_p), ("samples", C.c_void_p)]
+
+
 EVENT_SAMPLE_BYTES = 272  # INFW_EVENT_SAMPLE_BYTES: u32 perf raw size + raw sample (hdr, <= 256 B, pad)
 
 
@@ -162,6 +168,7 @@ ABI_SYMBOLS = [
     "infw_table_delete_batch", "infw_set_option", "infw_get_option", "infw_option_name", "infw_classify_variant",
     "infw_kernel_variant_name", "infw_classify_xdp", "infw_classify_xdp_mb", "infw_classify_xdp_mb_ex",
     "infw_events_capture_xdp", "infw_classify_xdp_host", "infw_classify_xdp_rings",
+    "infw_classify_xdp_rings_ex", "infw_events_capture_xdp_rings",
     "infw_pack_xdp_host", "infw_launch_counts", "infw_xdp_host_events", "infw_classify_bursts_host",
     "infw_pack_burst_host", "infw_burst_host_events",
 ]
@@ -267,6 +274,9 @@ _sig = {
     "infw_classify_xdp_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64]),
     "infw_pack_xdp_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, P(BatchSoaC)]),
     "infw_classify_xdp_rings": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), C.c_uint32, C.c_void_p]),
+    "infw_classify_xdp_rings_ex": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), C.c_uint32, P(XdpRingsEx), C.c_void_p]),
+    "infw_events_capture_xdp_rings": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), C.c_uint32, C.c_void_p, C.c_uint64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)

@@ -398,23 +398,55 @@ class Classifier:
             arr[i] = N.XdpRing(ptr(umem), ptr(descs), n, ifindex, 0, ptr(results), ptr(verdicts))
         check(N.lib.infw_classify_xdp_host(self._ctx, dev, arr, len(rings), chunk), "classify_xdp_host")
 
-    def classify_xdp_rings(self, rings, dev: int = 0, stream=None) -> None:
-        """infw_classify_xdp_rings: every multi-buffer ring of a poll in one asynchronous call — what classify_xdp_mb
-        computes ring by ring, with one scratch allocation and one set of launches.  `rings`: (umem, descs, n,
-        ifindex, results, verdicts) per ring, the tuple classify_xdp_host takes, as torch tensors in HBM or pinned
-        host memory (or raw addresses); results / verdicts may be None per ring.  No chain runs from one ring into
-        the next; no event stream."""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(torch.device("cuda", dev))
-        sp = stream if isinstance(stream, int) else stream.cuda_stream
-
+    @staticmethod
+    def _xdp_ring_array(rings):
         def ptr(x):
             return x if x is None or isinstance(x, int) else x.data_ptr()
         arr = (N.XdpRing * max(1, len(rings)))()
         for i, (umem, descs, n, ifindex, results, verdicts) in enumerate(rings):
             arr[i] = N.XdpRing(ptr(umem), ptr(descs), n, ifindex, 0, ptr(results), ptr(verdicts))
-        check(N.lib.infw_classify_xdp_rings(self._ctx, dev, arr, len(rings), sp), "classify_xdp_rings")
+        return arr
+
+    def classify_xdp_rings(self, rings, dev: int = 0, stream=None, *, events=None, events_count=None,
+                           samples=None) -> None:
+        """infw_classify_xdp_rings: every multi-buffer ring of a poll in one asynchronous call — what classify_xdp_mb
+        computes ring by ring, with one scratch allocation and one set of launches.  `rings`: (umem, descs, n,
+        ifindex, results, verdicts) per ring, the tuple classify_xdp_host takes, as torch tensors in HBM or pinned
+        host memory (or raw addresses); results / verdicts may be None per ring.  No chain runs from one ring into
+        the next.  events / events_count: the deny-event stream (infw_classify_xdp_rings_ex); a record's pkt_index is
+        the flat index of its frame's head (the sum of the n of the rings before its ring, plus its ring index), its
+        ifId the ring's own ifindex.  samples: also write the perf samples of the records this call appends (uint8
+        device tensor of (events capacity) x 272 B)."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(torch.device("cuda", dev))
+        sp = stream if isinstance(stream, int) else stream.cuda_stream
+        arr = self._xdp_ring_array(rings)
+        if events is None and samples is None:
+            check(N.lib.infw_classify_xdp_rings(self._ctx, dev, arr, len(rings), sp), "classify_xdp_rings")
+            return
+        cap = events.numel() // C.sizeof(N.EventRec) if events is not None else 0
+        assert samples is None or samples.numel() >= cap * N.EVENT_SAMPLE_BYTES, "samples: one 272-B slot per record"
+        ex = N.XdpRingsEx(C.sizeof(N.XdpRingsEx), 0, events.data_ptr() if events is not None else None, cap,
+                          events_count.data_ptr() if events_count is not None else None,
+                          samples.data_ptr() if samples is not None else None)
+        check(N.lib.infw_classify_xdp_rings_ex(self._ctx, dev, arr, len(rings), C.byref(ex), sp),
+              "classify_xdp_rings_ex")
+
+    def events_capture_xdp_rings(self, rings, events, events_count, samples, dev: int = 0, stream=None) -> None:
+        """infw_events_capture_xdp_rings: the perf samples of the deny events classify_xdp_rings(events=...) wrote,
+        over the same `rings` in the same order (results / verdicts are not used), each frame's first
+        min(length, 256) bytes gathered across its chain's buffers inside its own ring.  `samples` as for
+        events_capture_xdp."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(samples.device)
+        sp = stream if isinstance(stream, int) else stream.cuda_stream
+        cap = events.numel() // C.sizeof(N.EventRec)
+        assert samples.numel() >= cap * N.EVENT_SAMPLE_BYTES, "samples: one 272-B slot per event record"
+        check(N.lib.infw_events_capture_xdp_rings(self._ctx, dev, self._xdp_ring_array(rings), len(rings),
+                                                  events.data_ptr(), cap, events_count.data_ptr(),
+                                                  samples.data_ptr(), sp), "events_capture_xdp_rings")
 
     def classify_bursts_host(self, bursts, chunk: int = 0, dev: int = 0) -> None:
         """infw_classify_bursts_host (include/infw_host.h): DPDK-style bursts of frames in host memory — per burst a

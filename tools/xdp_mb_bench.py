@@ -10,6 +10,9 @@ plain calls, and infw_events_capture_xdp timed over the records the chains of 3 
 each ring its own umem in HBM and the interfaces of the workload in turn — (a) as R calls of infw_classify_xdp_mb and
 (b) as one infw_classify_xdp_rings, alternated over the same data (the answers are compared once); then one ring of
 --n descriptors through both calls.  Per arm: HIP events around the group and the host's wall-clock time of issuing it.
+With --events three more arms over the same rings, each with a deny-event buffer and sample slots for every descriptor:
+per ring infw_classify_xdp_mb_ex then infw_events_capture_xdp; one infw_classify_xdp_rings_ex with fused samples; one
+infw_classify_xdp_rings_ex then infw_events_capture_xdp_rings (the record counts of the three are compared once).
 
     python tools/xdp_mb_bench.py [--n 16777216] [--rounds 20] [--events] [--rings [64] --ring-n 2048]
 """
@@ -55,13 +58,34 @@ def rings_mode(args, clf, wl):
     def rings(out):
         return [(umem[r * M * STRIDE:(r + 1) * M * STRIDE], small[r * M:(r + 1) * M], M, ifs[r % len(ifs)],
                  out[r * M:(r + 1) * M], ver[r * M:(r + 1) * M]) for r in range(R)]
-    ra, rb = rings(res), rings(res2)
+    ra, rb, extra = rings(res), rings(res2), {}
     arms = {"per_ring_calls": lambda: [clf.classify_xdp_mb(u, d, m, i, results=o, verdicts=v) for u, d, m, i, o, v in ra],
             "one_rings_call": lambda: clf.classify_xdp_rings(rb),
             "large_xdp_mb": lambda: clf.classify_xdp_mb(umem, desc, n, ifs[0], results=res, verdicts=ver),
             "large_xdp_rings": lambda: clf.classify_xdp_rings([(umem, desc, n, ifs[0], res2, ver)])}
+    cnts = {}
+    if args.events:
+        rec, sb = C.sizeof(infw._native.EventRec), infw._native.EVENT_SAMPLE_BYTES
+        evb = {k: torch.zeros(R * M * rec, dtype=torch.uint8, device=dev) for k in "abc"}
+        smb = {k: torch.empty(R * M * sb, dtype=torch.uint8, device=dev) for k in "abc"}
+        cnts = {k: torch.zeros(R if k == "a" else 1, dtype=torch.int64, device=dev) for k in "abc"}
+
+        def per_ring_ev():
+            for r, (u, d, m, i, o, v) in enumerate(ra):
+                e, c = evb["a"][r * M * rec:(r + 1) * M * rec], cnts["a"][r:r + 1]
+                clf.classify_xdp_mb(u, d, m, i, results=o, verdicts=v, events=e, events_count=c)
+                clf.events_capture_xdp(u, d, m, e, c, smb["a"][r * M * sb:(r + 1) * M * sb])
+
+        def rings_ev_then_capture():
+            clf.classify_xdp_rings(rb, events=evb["c"], events_count=cnts["c"])
+            clf.events_capture_xdp_rings(rb, evb["c"], cnts["c"], smb["c"])
+        arms.update(per_ring_ev_capture=per_ring_ev, one_rings_ev_then_capture=rings_ev_then_capture,
+                    one_rings_ev_fused=lambda: clf.classify_xdp_rings(rb, events=evb["b"], events_count=cnts["b"],
+                                                                      samples=smb["b"]))
     dev_ms, host_ms = {k: [] for k in arms}, {k: [] for k in arms}
     for rnd in range(-3, args.rounds):  # three warm-up rounds
+        for c in cnts.values():  # each event arm appends to its own buffer, once per round
+            c.zero_()
         for k, fn in arms.items():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
@@ -76,9 +100,15 @@ def rings_mode(args, clf, wl):
             if rnd == -3 and k in ("one_rings_call", "large_xdp_rings"):
                 assert torch.equal(res, res2), k + ": differs from infw_classify_xdp_mb ring by ring"
                 res.fill_(-1), res2.fill_(-1)
+            if rnd == -3 and k == "one_rings_ev_fused":  # the last of the three event arms
+                assert int(cnts["a"].sum()) == int(cnts["b"]) == int(cnts["c"]) > 0, "event counts differ"
+                extra = {"event_records": int(cnts["b"])}
     stat = lambda t: {k: {"median": float(np.median(v)), "min": min(v), "max": max(v)} for k, v in t.items()}
     d, h = stat(dev_ms), stat(host_ms)
-    print(json.dumps({"rings": R, "ring_n": M, "n_large": n, "rounds": args.rounds,
+    if args.events:
+        extra.update({"per_ring_ev_over_fused_" + w: t["per_ring_ev_capture"]["median"] / t["one_rings_ev_fused"]["median"]
+                      for w, t in (("event", d), ("host", h))})
+    print(json.dumps({**extra, "rings": R, "ring_n": M, "n_large": n, "rounds": args.rounds,
                       "kernel": clf.variant(infw.INPUT_FRAMES), "event_ms": d, "host_issue_ms": h,
                       "per_ring_over_one_call_event": d["per_ring_calls"]["median"] / d["one_rings_call"]["median"],
                       "per_ring_over_one_call_host": h["per_ring_calls"]["median"] / h["one_rings_call"]["median"],
