@@ -468,6 +468,41 @@ int infw_classify_xdp_host(infw_ctx *ctx, int dev, const struct infw_xdp_ring *r
 #define INFW_XDP_RINGS_MAX 1024
 int infw_classify_xdp_rings(infw_ctx *ctx, int dev, const struct infw_xdp_ring *rings, uint32_t n_rings,
                             void *stream);
+/* infw_classify_xdp_rings plus the step a daemon takes next, on the device:    */
+/* every ring partitioned by its frames' verdicts into a forward list and a    */
+/* fill list.  With the same `rings` it computes what infw_classify_xdp_rings  */
+/* computes (result words, verdicts, counters, each frame counted once, a      */
+/* ring's NULL results or verdicts skipped — both may be NULL: the call then   */
+/* classifies and splits only) and, on the same stream against the same epoch, */
+/* for ring r:                                                                 */
+/*   - split[r].pass[0 .. n_pass[r]): the descriptors of ring r whose frame's  */
+/*     verdict is INFW_XDP_PASS, in ring order, copied verbatim (addr, len,    */
+/*     options).  Every descriptor of a chain has its head's verdict, so       */
+/*     chains stay whole and contiguous; a chain left open at the ring's last  */
+/*     descriptor is copied as it is;                                          */
+/*   - split[r].fill[0 .. rings[r].n - n_pass[r]): addr & (2^48 - 1)           */
+/*     (xsk_umem__extract_addr; the kernel masks it to the chunk in aligned    */
+/*     mode) of every other descriptor — DROP and ABORTED — in ring order;     */
+/*   - n_pass[r], written for every r: 0 for a ring with n == 0;               */
+/*   - a NULL pass or fill skips that list for that ring only, its count is    */
+/*     still written; slots at or past the counts are not written.             */
+/* pass, fill and n_pass are device-writable; pass 16-byte, fill 8-byte,       */
+/* n_pass 4-byte aligned; a ring's lists hold rings[r].n slots each.  `rings`  */
+/* and `split` are ordinary host arrays, free when the call returns;           */
+/* asynchronous, no host-side wait.  Errnos as infw_classify_xdp_rings, plus   */
+/* -EINVAL for a NULL split or n_pass with n_rings > 0 and for a misaligned    */
+/* pass or fill in a ring with n > 0.  -ENOMEM: the scratch of                 */
+/* infw_classify_xdp_rings plus 8 B per chunk (its pass mask), 32 B per        */
+/* non-empty ring (the output table) and 4 B, each array rounded up to 16 B.   */
+/* Nothing is launched when an error is returned (n_pass is not zeroed         */
+/* either); n_rings == 0 returns 0.                                            */
+struct infw_xdp_ring_split {             /* one per ring, same order as rings[] */
+    struct infw_xdp_desc *pass;          /* rings[r].n slots, 16-B aligned, or NULL */
+    uint64_t *fill;                      /* rings[r].n slots, 8-B aligned, or NULL  */
+};
+int infw_classify_xdp_rings_split(infw_ctx *ctx, int dev, const struct infw_xdp_ring *rings,
+                                  const struct infw_xdp_ring_split *split, uint32_t n_rings,
+                                  uint32_t *n_pass /* device, n_rings words */, void *stream);
 /* The host packer of infw_classify_xdp_host alone, on the calling thread: one */
 /* ring's frames -> the family-compact streams in host memory (the layout       */
 /* infw_classify_c reads; out->ifindex may be NULL, else it is filled with      */

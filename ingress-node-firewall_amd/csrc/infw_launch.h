@@ -52,6 +52,19 @@ struct infw_xdp_ring_ent {
     uint32_t n, ifindex, chunk0, flat0;
 };
 #define INFW_XDP_RINGS_GROUP 64
+// infw_classify_xdp_rings_split: the output side of one ring, parallel to its infw_xdp_ring_ent — the caller's forward
+// and fill lists and the caller's ring index (the table holds the non-empty rings only; n_pass is indexed by the
+// caller's).  24 B padded to 32: two 16-B words per entry, and 64 of them fit one upload kernel's arguments.
+struct infw_xdp_split_ent {
+    infw_xdp_desc *pass;
+    uint64_t *fill;
+    uint32_t ring, pad[3];
+};
+struct infw_xdp_split_args {
+    const infw_xdp_split_ent *ents;  // one per entry of the ring table, same order
+    uint32_t *n_pass;                // device, n_rings words: zeroed, then one word per non-empty ring
+    uint32_t n_rings;                // the caller's ring count, empty rings included
+};
 
 extern "C" {
 // Launch (asynchronous).  0, or -EIO on a launch error.
@@ -77,8 +90,11 @@ int infw_launch_classify_xdp_mb(const infw_launch_args *a);
 // With a->ev_count (infw_classify_xdp_rings_ex) the records this call appended get pkt_index = the flat index of the
 // frame's head (ents[r].flat0 + i) and ifId from the ring's own ifindex; with `samples` too, their perf samples are
 // written from the table already in scratch (slots [count before, min(count after, a->ev_cap)), no others).
+// With `split` (infw_classify_xdp_rings_split; null: the launches and the scratch are the plain call's) n_pass is
+// zeroed on the stream first — also when n_ents == 0 — and after the frames kernel each ring is partitioned by its
+// frames' verdicts into split->ents[r].pass / .fill, n_pass[split->ents[r].ring] = the ring's passed descriptors.
 int infw_launch_classify_xdp_rings(const infw_launch_args *a, const infw_xdp_ring_ent *ents, uint32_t n_ents,
-                                   uint32_t n_chunks, infw_event_sample *samples);
+                                   uint32_t n_chunks, infw_event_sample *samples, const infw_xdp_split_args *split);
 // infw_events_capture_xdp_rings (xdpchain.hip): samples[k] for k < min(*count, cap) over the same `ents` (total = the
 // sum of their n): a record's ring is found from its flat pkt_index, its chain walked inside that ring.  One
 // allocation from `pool` (48 B per entry).  Asynchronous.  0, -EIO, -ENOMEM.

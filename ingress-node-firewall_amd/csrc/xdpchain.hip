@@ -32,6 +32,8 @@
 // ring table and a chunk -> ring map in scratch — the xdp_rings_* kernels below.  Their deny events
 // (infw_classify_xdp_rings_ex) carry the flat index of the frame's head; xdp_rings_event_samples finds each record's
 // ring in the table's flat-index column (staged in LDS, two wave-wide compares) and walks the chain inside that ring.
+// The output side of a poll (infw_classify_xdp_rings_split): each ring partitioned by verdict into its forward and fill
+// lists after the frames kernel — the xdp_rings_split_* kernels, a second run of xdp_chain_carry between them.
 #include <hip/hip_runtime.h>
 #include <errno.h>
 #include <stdint.h>
@@ -457,6 +459,108 @@ __global__ __launch_bounds__(64 * kRingWaves) void xdp_rings_scatter(const infw_
     }
 }
 
+// ---- infw_classify_xdp_rings_split: every ring partitioned by its frames' verdicts --------------------------------
+//
+// After the frames kernel: ring r's descriptors whose frame passed go to pass_r in ring order (16 B each, verbatim),
+// the umem address of every other one to fill_r, and the pass count to n_pass[r] — a segmented, stable partition over
+// the same chunks, with the same forward-only shape as the chain pass (no workgroup waits on another):
+//
+//   xdp_rings_split_upload  the output table {pass, fill, caller's ring index} beside the ring table, 64 entries per
+//                      launch by value; its first launch also zeroes n_pass (an empty ring has no entry and reads 0)
+//   xdp_rings_split_count   per chunk the two gathers fver[frame_of[flat0 + i]] once: one ballot of verdict == PASS is
+//                      the chunk's pass mask (lanes past n clear), kept in scratch (8 B per chunk); the workgroup's
+//                      summary is {ring starts among its chunks, passes since the last of them} — chain_op's monoid,
+//                      exact because a ring starts on a chunk boundary
+//   xdp_chain_carry    as it is, over those summaries -> per workgroup the passes its open ring already has
+//   xdp_rings_split_write   per chunk: base = the carry folded with the earlier waves of the workgroup through LDS (0 in
+//                      a ring's first chunk), rank = popcount(mask & lanes below); a pass lane stores its descriptor
+//                      to pass[base + rank], any other lane addr & (2^48 - 1) to fill[i - base - rank]; the wave of a
+//                      ring's last chunk writes n_pass
+struct SplitGroup {
+    infw_xdp_split_ent e[kRingGroup];
+};
+static_assert(sizeof(infw_xdp_split_ent) == 32, "two 16-B words per entry");
+
+__global__ __launch_bounds__(kRingGroup) void xdp_rings_split_upload(const SplitGroup g, uint32_t cnt,
+                                                                      infw_xdp_split_ent *__restrict__ table,
+                                                                      uint32_t *__restrict__ n_pass, uint32_t n_zero) {
+    if (threadIdx.x < cnt) table[threadIdx.x] = g.e[threadIdx.x];
+    for (uint32_t r = threadIdx.x; r < n_zero; r += kRingGroup) n_pass[r] = 0;
+}
+
+__global__ __launch_bounds__(64 * kRingWaves) void xdp_rings_split_count(const infw_xdp_ring_ent *__restrict__ table,
+                                                                          const uint32_t *__restrict__ chunk_ring,
+                                                                          uint32_t n_chunks,
+                                                                          const uint32_t *__restrict__ frame_of,
+                                                                          const uint8_t *__restrict__ fver,
+                                                                          uint64_t *__restrict__ masks,
+                                                                          uint2 *__restrict__ sums) {
+    __shared__ uint2 s_w[kRingWaves];
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t c = blockIdx.x * kRingWaves + wv;
+    uint64_t i;
+    const infw_xdp_ring_ent e = ring_of_chunk(table, chunk_ring, c, n_chunks, i);  // past the last chunk: n == 0
+    bool pass = false;
+    if (i < e.n) {
+        const uint32_t f = __builtin_nontemporal_load(&frame_of[e.flat0 + i]);
+        pass = __builtin_nontemporal_load(&fver[f]) == INFW_XDP_PASS;
+    }
+    const uint64_t m = __ballot(pass);
+    if ((threadIdx.x & 63u) == 0) {
+        if (c < n_chunks) masks[c] = m;
+        s_w[wv] = make_uint2(c < n_chunks && c == e.chunk0 ? 1u : 0u, (uint32_t)__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint2 t = s_w[0];
+        for (int w = 1; w < kRingWaves; w++) t = chain_op(t, s_w[w]);
+        sums[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(64 * kRingWaves) void xdp_rings_split_write(const infw_xdp_ring_ent *__restrict__ table,
+                                                                          const infw_xdp_split_ent *__restrict__ outs,
+                                                                          const uint32_t *__restrict__ chunk_ring,
+                                                                          uint32_t n_chunks,
+                                                                          const uint64_t *__restrict__ masks,
+                                                                          const uint2 *__restrict__ sums,
+                                                                          uint32_t *__restrict__ n_pass) {
+    __shared__ uint2 s_w[kRingWaves];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t c = blockIdx.x * kRingWaves + wv;
+    const bool live = c < n_chunks;  // wave-uniform
+    infw_xdp_ring_ent e{};
+    infw_xdp_split_ent o{};
+    uint64_t m = 0;
+    if (live) {
+        const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk_ring[c]);
+        e = table[r];
+        o = outs[r];
+        m = masks[c];
+    }
+    const bool start = live && c == e.chunk0;
+    if (lane == 0) s_w[wv] = make_uint2(start ? 1u : 0u, (uint32_t)__popcll(m));
+    __syncthreads();
+    if (!live) return;
+    uint2 pre = sums[blockIdx.x];  // {ring starts before the workgroup's chunks, passes of the ring open at their start}
+    for (uint32_t w = 0; w < wv; w++) pre = chain_op(pre, s_w[w]);
+    const uint32_t base = start ? 0u : pre.y;  // passed descriptors of this ring before this chunk
+    const uint32_t first = (c - e.chunk0) * 64u;  // < n: the ring owns exactly ceil(n / 64) chunks
+    const uint32_t i = first + lane;
+    if (i < e.n) {
+        const u32x4 d = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(e.descs) + i);
+        const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (m >> lane & 1ull) {
+            if (o.pass) __builtin_nontemporal_store(d, reinterpret_cast<u32x4 *>(o.pass) + (base + rank));
+        } else if (o.fill) {
+            const uint64_t addr = ((uint64_t)d[1] << 32 | d[0]) & ((1ull << 48) - 1);
+            __builtin_nontemporal_store(addr, &o.fill[i - base - rank]);
+        }
+    }
+    if (lane == 0 && e.n - first <= 64u) n_pass[o.ring] = base + (uint32_t)__popcll(m);
+}
+
 // ---- infw_classify_xdp_rings_ex / infw_events_capture_xdp_rings: perf samples over the rings of one call ----------
 //
 // A record's pkt_index is the flat index of its frame's head (the ring's first flat index + i), so the sample kernel
@@ -594,16 +698,25 @@ static void launch_rings_samples(const infw_xdp_ring_ent *table, uint32_t n_ents
 // ents: the call's non-empty rings with their first chunk and first flat index filled in (abi.cpp), read before the
 // call returns; a->n is the sum of their n (< 2^31), n_chunks the sum of their chunks.
 extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const infw_xdp_ring_ent *ents, uint32_t n_ents,
-                                              uint32_t n_chunks, infw_event_sample *samples) {
+                                              uint32_t n_chunks, infw_event_sample *samples,
+                                              const infw_xdp_split_args *split) {
     const uint64_t n = a->n;
-    if (n == 0 || n_ents == 0) return 0;
+    if (n == 0 || n_ents == 0) {
+        if (!split || split->n_rings == 0) return 0;
+        hipLaunchKernelGGL(xdp_rings_split_upload, dim3(1), dim3(kRingGroup), 0, a->stream, SplitGroup{}, 0u,
+                           (infw_xdp_split_ent *)nullptr, split->n_pass, split->n_rings);  // only empty rings: the zeros
+        return hipGetLastError() == hipSuccess ? 0 : -EIO;
+    }
     const uint32_t n_tiles = (n_chunks + kRingWaves - 1) / kRingWaves;
     const bool events = a->ev_count != nullptr;
     bool any_res = false, any_ver = false;
     for (uint32_t r = 0; r < n_ents; r++) any_res |= ents[r].results != nullptr, any_ver |= ents[r].verdicts != nullptr;
     // one stream-ordered allocation, carved at 16-B boundaries: 29 B per descriptor as for one ring, 4 B per chunk
     // (its ring), 8 B per workgroup of kRingWaves chunks (its summary), 48 B per ring (the table) and the frame count;
-    // with the event stream 4 B more per descriptor (head_of) and the count's snapshot
+    // with the event stream 4 B more per descriptor (head_of) and the count's snapshot.  With the split, behind all of
+    // those (without it the carve is the plain call's): 8 B per chunk (its pass mask), 32 B per ring (the output table)
+    // and the second carry's total.  The split's per-workgroup summaries reuse `tiles`: xdp_rings_emit, the chain
+    // pass's last reader of it, has run before the frames kernel, and the split passes run after.
     size_t bytes = 0;
     auto carve = [&](size_t sz) {
         const size_t at = bytes;
@@ -614,7 +727,8 @@ extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const i
                  o_fof = carve(n * 4), o_res = carve(n * 4), o_ver = carve(n), o_tiles = carve((size_t)n_tiles * 8),
                  o_nf = carve(4), o_map = carve((size_t)n_chunks * 4),
                  o_tab = carve((size_t)n_ents * sizeof(infw_xdp_ring_ent)), o_hof = carve(events ? n * 4 : 0),
-                 o_evb = carve(events ? 8 : 0);
+                 o_evb = carve(events ? 8 : 0), o_mask = carve(split ? (size_t)n_chunks * 8 : 0),
+                 o_out = carve(split ? (size_t)n_ents * sizeof(infw_xdp_split_ent) : 0), o_nst = carve(split ? 4 : 0);
     uint8_t *sc = nullptr;
     if (!a->pool || hipMallocFromPoolAsync(reinterpret_cast<void **>(&sc), bytes, a->pool, a->stream) != hipSuccess) {
         (void)hipGetLastError();
@@ -634,6 +748,16 @@ extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const i
     const uint8_t *umem0 = ents[0].umem;
 
     upload_ring_table(ents, n_ents, table, a->stream);
+    infw_xdp_split_ent *outs = reinterpret_cast<infw_xdp_split_ent *>(sc + o_out);
+    if (split) {
+        SplitGroup grp{};
+        for (uint32_t base = 0; base < n_ents; base += kRingGroup) {
+            const uint32_t cnt = n_ents - base < (uint32_t)kRingGroup ? n_ents - base : (uint32_t)kRingGroup;
+            for (uint32_t k = 0; k < cnt; k++) grp.e[k] = split->ents[base + k];
+            hipLaunchKernelGGL(xdp_rings_split_upload, dim3(1), dim3(kRingGroup), 0, a->stream, grp, cnt, outs + base,
+                               split->n_pass, base ? 0u : split->n_rings);
+        }
+    }
     hipLaunchKernelGGL(xdp_rings_map, dim3((n_chunks + 255) / 256), dim3(256), 0, a->stream,
                        (const infw_xdp_ring_ent *)table, n_ents, n_chunks, chunk_ring);
     hipLaunchKernelGGL(xdp_rings_reduce, dim3(n_tiles), dim3(64 * kRingWaves), 0, a->stream,
@@ -653,7 +777,7 @@ extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const i
         f.umem = nullptr;
         f.xdp = nullptr;
         f.results = any_res ? fres : nullptr;
-        f.verdicts = any_ver ? fver : nullptr;
+        f.verdicts = any_ver || split ? fver : nullptr;  // the split reads the frame verdicts whoever else does
         rc = infw_launch_classify(&f);
     }
     if (rc == 0 && events && a->ev_cap) {  // at most one new record per frame, and none past the capacity
@@ -672,6 +796,19 @@ extern "C" int infw_launch_classify_xdp_rings(const infw_launch_args *a, const i
         hipLaunchKernelGGL(xdp_rings_scatter, dim3(n_tiles < cap ? n_tiles : cap), dim3(64 * kRingWaves), 0, a->stream,
                            (const infw_xdp_ring_ent *)table, (const uint32_t *)chunk_ring, n_chunks,
                            (const uint32_t *)cf.frame_of, (const uint32_t *)fres, (const uint8_t *)fver);
+        if (hipGetLastError() != hipSuccess) rc = -EIO;
+    }
+    if (rc == 0 && split) {
+        uint64_t *masks = reinterpret_cast<uint64_t *>(sc + o_mask);
+        hipLaunchKernelGGL(xdp_rings_split_count, dim3(n_tiles), dim3(64 * kRingWaves), 0, a->stream,
+                           (const infw_xdp_ring_ent *)table, (const uint32_t *)chunk_ring, n_chunks,
+                           (const uint32_t *)cf.frame_of, (const uint8_t *)fver, masks, tiles);
+        hipLaunchKernelGGL(xdp_chain_carry, dim3(1), dim3(kCarry), 0, a->stream, tiles, n_tiles,
+                           reinterpret_cast<uint32_t *>(sc + o_nst));
+        hipLaunchKernelGGL(xdp_rings_split_write, dim3(n_tiles), dim3(64 * kRingWaves), 0, a->stream,
+                           (const infw_xdp_ring_ent *)table, (const infw_xdp_split_ent *)outs,
+                           (const uint32_t *)chunk_ring, n_chunks, (const uint64_t *)masks, (const uint2 *)tiles,
+                           split->n_pass);
         if (hipGetLastError() != hipSuccess) rc = -EIO;
     }
     (void)hipFreeAsync(sc, a->stream);

@@ -101,6 +101,11 @@ class XdpRing(C.Structure):
                 ("flags", C.c_uint32), ("results", C.c_void_p), ("verdicts", C.c_void_p)]
 
 
+class XdpRingSplit(C.Structure):
+    """struct infw_xdp_ring_split (include/infw.h): one ring's forward and fill lists (infw_classify_xdp_rings_split)."""
+    _fields_ = [("pass_", C.c_void_p), ("fill", C.c_void_p)]
+
+
 class FrameBurst(C.Structure):
     """struct infw_frame_burst (include/infw_host.h): a DPDK-style burst of frames in host memory, one pointer each."""
     _fields_ = [("frames", C.c_void_p), ("linear_len", C.c_void_p), ("pkt_len", C.c_void_p), ("n", C.c_uint64),
@@ -168,7 +173,7 @@ ABI_SYMBOLS = [
     "infw_table_delete_batch", "infw_set_option", "infw_get_option", "infw_option_name", "infw_classify_variant",
     "infw_kernel_variant_name", "infw_classify_xdp", "infw_classify_xdp_mb", "infw_classify_xdp_mb_ex",
     "infw_events_capture_xdp", "infw_classify_xdp_host", "infw_classify_xdp_rings",
-    "infw_classify_xdp_rings_ex", "infw_events_capture_xdp_rings",
+    "infw_classify_xdp_rings_ex", "infw_events_capture_xdp_rings", "infw_classify_xdp_rings_split",
     "infw_pack_xdp_host", "infw_launch_counts", "infw_xdp_host_events", "infw_classify_bursts_host",
     "infw_pack_burst_host", "infw_burst_host_events",
 ]
@@ -277,6 +282,8 @@ _sig = {
     "infw_classify_xdp_rings_ex": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), C.c_uint32, P(XdpRingsEx), C.c_void_p]),
     "infw_events_capture_xdp_rings": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), C.c_uint32, C.c_void_p, C.c_uint64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infw_classify_xdp_rings_split": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), P(XdpRingSplit), C.c_uint32,
+                                                C.c_void_p, C.c_void_p]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)
@@ -344,6 +351,7 @@ for _name, (_res, _args) in _wsig.items():
     _f.argtypes = _args
 
 assert C.sizeof(EventHdrSt) == 8 and C.sizeof(EventRec) == 24 and C.sizeof(XdpRing) == 48
+assert C.sizeof(XdpRingSplit) == 16
 if lib.infw_abi_version() != ABI_VERSION:
     raise ImportError(f"{LIB_PATH}: ABI {lib.infw_abi_version()}, these bindings are ABI {ABI_VERSION}: rebuild (make)")
 

@@ -433,6 +433,26 @@ class Classifier:
         check(N.lib.infw_classify_xdp_rings_ex(self._ctx, dev, arr, len(rings), C.byref(ex), sp),
               "classify_xdp_rings_ex")
 
+    def classify_xdp_rings_split(self, rings, split, n_pass, dev: int = 0, stream=None) -> None:
+        """infw_classify_xdp_rings_split: classify_xdp_rings over `rings`, and each ring partitioned on the device by
+        its frames' verdicts.  `split`: (pass, fill) per ring — pass an int32 / uint8 device tensor of n 16-B
+        descriptor slots, fill an int64 one of n slots, either None — in the order of `rings`; `n_pass`: int32 device
+        tensor of len(rings) words.  Afterwards pass[:n_pass[r]] holds ring r's descriptors with verdict XDP_PASS in
+        ring order (chains whole), fill[:n - n_pass[r]] the umem address (addr & (2^48 - 1)) of every other one."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(torch.device("cuda", dev))
+        sp = stream if isinstance(stream, int) else stream.cuda_stream
+        ptr = lambda x: x if x is None or isinstance(x, int) else x.data_ptr()
+        assert split is None or len(split) == len(rings), "split: one (pass, fill) per ring"
+        arr = None
+        if split is not None:
+            arr = (N.XdpRingSplit * max(1, len(split)))()
+            for i, (p, f) in enumerate(split):
+                arr[i] = N.XdpRingSplit(ptr(p), ptr(f))
+        check(N.lib.infw_classify_xdp_rings_split(self._ctx, dev, self._xdp_ring_array(rings), arr, len(rings),
+                                                  ptr(n_pass), sp), "classify_xdp_rings_split")
+
     def events_capture_xdp_rings(self, rings, events, events_count, samples, dev: int = 0, stream=None) -> None:
         """infw_events_capture_xdp_rings: the perf samples of the deny events classify_xdp_rings(events=...) wrote,
         over the same `rings` in the same order (results / verdicts are not used), each frame's first

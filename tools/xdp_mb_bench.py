@@ -13,8 +13,12 @@ each ring its own umem in HBM and the interfaces of the workload in turn — (a)
 With --events three more arms over the same rings, each with a deny-event buffer and sample slots for every descriptor:
 per ring infw_classify_xdp_mb_ex then infw_events_capture_xdp; one infw_classify_xdp_rings_ex with fused samples; one
 infw_classify_xdp_rings_ex then infw_events_capture_xdp_rings (the record counts of the three are compared once).
+With --split two more arms over the same rings: one infw_classify_xdp_rings_split (forward and fill lists written on the
+device), and infw_classify_xdp_rings followed by what a host does without it — a D2H of the verdict bytes, a wait, and
+one numpy boolean index per ring and list on one thread (a C loop would be faster than this host form); its issue time
+is the whole step.  The lists of the two are compared once.
 
-    python tools/xdp_mb_bench.py [--n 16777216] [--rounds 20] [--events] [--rings [64] --ring-n 2048]
+    python tools/xdp_mb_bench.py [--n 16777216] [--rounds 20] [--events] [--rings [64] --ring-n 2048 [--split]]
 """
 import ctypes as C
 import argparse
@@ -82,6 +86,27 @@ def rings_mode(args, clf, wl):
         arms.update(per_ring_ev_capture=per_ring_ev, one_rings_ev_then_capture=rings_ev_then_capture,
                     one_rings_ev_fused=lambda: clf.classify_xdp_rings(rb, events=evb["b"], events_count=cnts["b"],
                                                                       samples=smb["b"]))
+    if args.split:
+        sp = torch.full((R * M, 4), -1, dtype=torch.int32, device=dev)
+        sf = torch.full((R * M,), -1, dtype=torch.int64, device=dev)
+        sn = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        lists = [(sp[r * M:(r + 1) * M], sf[r * M:(r + 1) * M]) for r in range(R)]
+        desc_h = small.cpu().numpy()  # the host's own view of its rings, as a daemon has it
+        addr_h = np.ascontiguousarray(desc_h[:, :2]).view(np.int64).ravel() & ((1 << 48) - 1)
+        ver_h, host_out = torch.empty(R * M, dtype=torch.uint8).pin_memory(), {}
+
+        def rings_then_host_split():
+            clf.classify_xdp_rings(rb)
+            ver_h.copy_(ver[:R * M], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            v = ver_h.numpy() == infw.XDP_PASS
+            host_out["pass"] = [desc_h[r * M:(r + 1) * M][v[r * M:(r + 1) * M]] for r in range(R)]
+            host_out["fill"] = [addr_h[r * M:(r + 1) * M][~v[r * M:(r + 1) * M]] for r in range(R)]
+        # beside the plain small-rings arms, ahead of the 2^24-descriptor ones: an arm that follows those pays ~0.3 ms
+        # more to issue (their 0.5-GB scratch blocks are then what the pool has to cut its 4 MB from — supposed)
+        head = {k: arms.pop(k) for k in ("per_ring_calls", "one_rings_call")}
+        arms = {**head, "one_rings_split_call": lambda: clf.classify_xdp_rings_split(rb, lists, sn),
+                "one_rings_call_host_split": rings_then_host_split, **arms}
     dev_ms, host_ms = {k: [] for k in arms}, {k: [] for k in arms}
     for rnd in range(-3, args.rounds):  # three warm-up rounds
         for c in cnts.values():  # each event arm appends to its own buffer, once per round
@@ -100,6 +125,13 @@ def rings_mode(args, clf, wl):
             if rnd == -3 and k in ("one_rings_call", "large_xdp_rings"):
                 assert torch.equal(res, res2), k + ": differs from infw_classify_xdp_mb ring by ring"
                 res.fill_(-1), res2.fill_(-1)
+            if rnd == -3 and k == "one_rings_call_host_split":  # after the device split: the same lists
+                cnt, gp, gf = sn.cpu().numpy(), sp.cpu().numpy(), sf.cpu().numpy()
+                for r in range(R):
+                    assert cnt[r] == len(host_out["pass"][r]) and 0 < cnt[r] < M, "split: pass counts"
+                    assert np.array_equal(gp[r * M:r * M + cnt[r]], host_out["pass"][r]), "split: pass lists differ"
+                    assert np.array_equal(gf[r * M:(r + 1) * M - cnt[r]], host_out["fill"][r]), "split: fill lists"
+                extra = {**extra, "passed": int(cnt.sum())}
             if rnd == -3 and k == "one_rings_ev_fused":  # the last of the three event arms
                 assert int(cnts["a"].sum()) == int(cnts["b"]) == int(cnts["c"]) > 0, "event counts differ"
                 extra = {"event_records": int(cnts["b"])}
@@ -124,6 +156,7 @@ def main():
     ap.add_argument("--events", action="store_true")
     ap.add_argument("--rings", type=int, nargs="?", const=64, default=0)
     ap.add_argument("--ring-n", type=int, default=2048)
+    ap.add_argument("--split", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     n, dev = args.n, torch.device("cuda", 0)
