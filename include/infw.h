@@ -295,7 +295,8 @@ int infw_get_launch(infw_ctx *ctx, int *block, int *scan_group, int *blocks_per_
 /*   d16              -1 auto, 0 off, 1 on: /16 words in front of DIR-24-8      */
 /*   dt_half          -1 auto, 0 off, 1 on: half-first decision-line reads      */
 /*   dt_parts         0 auto, or 1|2|4|8|16 value parts per (list, class)        */
-/*   dt_adapt         1 per-list part counts (<= 4096 lists), 0 uniform parts    */
+/*   dt_adapt         1 per-list cut codes (<= 4096 lists), 2 the same without  */
+/*                    the skewed cuts, 0 uniform parts                           */
 /*   dt_budget_mb     64..1048576 (2048): entry lines of one image at most        */
 /*   compile_threads  0 hardware threads (<= 16), or 1..16                        */
 /*   split            -1 auto, 0 off, 1 on: two-phase classify (many lists)       */

@@ -246,10 +246,15 @@ __device__ __forceinline__ uint32_t dt_lookup_at(const infw_dt_line *__restrict_
                                                  uint64_t slot, uint32_t v) {
     return kHalf ? dt_lookup_half(dte, dtl, slot, v) : dt_lookup_full(dte, dtl, slot, v);
 }
+// Entry line of (list, cls, v) under cut code p.  coded (wave-uniform): the epoch has per-list cut codes; without
+// them p is the uniform plog2 and the skewed codes' select (infw_dt_cut_line) is not computed.
+__device__ __forceinline__ uint64_t dt_slot(bool coded, uint32_t list, int cls, uint32_t v, uint32_t plog2, uint32_t p) {
+    return coded ? infw_dt_slot_p(list, cls, v, plog2, p) : infw_dt_slot(list, cls, v, plog2);
+}
 template <bool kHalf = false>
 __device__ __forceinline__ uint32_t dt_lookup(const infw_dt_line *__restrict__ dte, const infw_dt_line *__restrict__ dtl,
-                                              uint32_t list, int cls, uint32_t v, uint32_t plog2, uint32_t p) {
-    return dt_lookup_at<kHalf>(dte, dtl, infw_dt_slot_p(list, cls, v, plog2, p), v);
+                                              bool coded, uint32_t list, int cls, uint32_t v, uint32_t plog2, uint32_t p) {
+    return dt_lookup_at<kHalf>(dte, dtl, dt_slot(coded, list, cls, v, plog2, p), v);
 }
 
 // Longest /33../128 prefix covering an IPv6 address (infw_v6_long, device form):
@@ -831,7 +836,7 @@ __global__ __launch_bounds__(kBlock, kWaves) void classify_kernel(const infw_dev
                     uint32_t p = T.dt_plog2;
                     if (kPl) p = infw_dt_parts_of(s_pl[(lst - 1) & (INFW_DT_PL_LISTS - 1)], lst - 1, INFW_DT_PL_LISTS, cls, p);
                     else if (T.n_dt_pl && lst - 1 < T.n_dt_pl) p = (T.dt_pl[lst - 1] >> (3 * cls)) & 7u;
-                    w = split_word(infw_dt_slot_p(lst - 1, cls, val, T.dt_plog2, p), val, plen);
+                    w = split_word(dt_slot(kPl || T.n_dt_pl, lst - 1, cls, val, T.dt_plog2, p), val, plen);
                 }
                 __builtin_nontemporal_store(w, &in.mid[i]);
             }
@@ -844,7 +849,7 @@ __global__ __launch_bounds__(kBlock, kWaves) void classify_kernel(const infw_dev
             uint32_t p = T.dt_plog2;
             if (kPl) p = infw_dt_parts_of(s_pl[(lst - 1) & (INFW_DT_PL_LISTS - 1)], lst - 1, INFW_DT_PL_LISTS, cls, p);
             else if (T.n_dt_pl && lst - 1 < T.n_dt_pl) p = (T.dt_pl[lst - 1] >> (3 * cls)) & 7u;
-            result = dt_lookup<kHalf>(T.dte, T.dtl, lst - 1, cls, val, T.dt_plog2, p);
+            result = dt_lookup<kHalf>(T.dte, T.dtl, kPl || T.n_dt_pl, lst - 1, cls, val, T.dt_plog2, p);
         }
         // ---- first match, one lane per rule, G packets in flight
         uint64_t pending = G == 0 ? 0 : __ballot(cnt != 0);

@@ -30,7 +30,7 @@ namespace infw {
 namespace {
 
 constexpr char kMagic[8] = {'I', 'N', 'F', 'W', 'I', 'M', 'G', '1'};
-constexpr uint32_t kFormat = 2;  // 2: payload hash in the header
+constexpr uint32_t kFormat = 3;  // 2: payload hash in the header; 3: skewed cut codes 5..7 in dt_pl
 
 // XXH64 (seed 0) of the payload, the published xxHash 64-bit algorithm — tests recompute it with the xxhash module.
 constexpr uint64_t kP1 = 0x9E3779B185EBCA87ull, kP2 = 0xC2B2AE3D27D4EB4Full, kP3 = 0x165667B19E3779F9ull,
@@ -275,7 +275,8 @@ bool check_tables(const HostTables &h, const IncState &inc, uint64_t n_vals, std
         if (h.dt_pl.size() != INFW_DT_PL_LISTS) return bad("part-count table size");
         for (uint32_t w : h.dt_pl)
             for (int c = 0; c < INFW_NCLS; c++)
-                if (((w >> (3 * c)) & 7u) > h.dt_plog2) return bad("part count above the image's");
+                if (((w >> (3 * c)) & 7u) > (h.dt_plog2 == 4 ? 7u : h.dt_plog2))  // 5..7: skewed, 16-line regions only
+                    return bad("part count above the image's");
     }
     for (const infw_dt_line &l : h.dte)
         if (l.w[0] & INFW_DT_ROOT) {

@@ -292,10 +292,12 @@ int patch_tables(const PendingMap &m, HostTables &h, IncState &inc, std::vector<
         if (h.desc.size() < (size_t)(lid + 1) * INFW_DESC_STRIDE) h.desc.resize((size_t)(lid + 1) * INFW_DESC_STRIDE, 0);
         const size_t per_list = (size_t)INFW_NCLS << h.dt_plog2;
         if (h.dte.size() < (lid + 1) * per_list) h.dte.resize((lid + 1) * per_list, infw_dt_line{});
-        // a list past the part-count table keeps uniform parts (infw_dt_parts_of)
+        // a list past the part-count table keeps uniform parts (infw_dt_parts_of); one inside it gets its cut
+        // codes from the full compile's chooser
         const bool pl = lid < h.dt_pl.size();
         int rc = compile_rule_list(m.pool.vals[vid].data(), h.rules, &h.desc[(size_t)lid * INFW_DESC_STRIDE],
-                                   &h.dte[lid * per_list], h.dtl, h.dt_plog2, pl ? &h.dt_pl[lid] : nullptr);
+                                   &h.dte[lid * per_list], h.dtl, h.dt_plog2, pl ? &h.dt_pl[lid] : nullptr,
+                                   opt.dt_adapt == 1);
         if (pl) mark(ranges, TB_DTPL, (uint64_t)lid * 4, 4);
         if (rc) {
             inc.valid = false;  // the image is no longer trustworthy: the next commit recompiles

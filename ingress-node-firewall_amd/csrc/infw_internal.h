@@ -248,7 +248,8 @@ struct Options {
     int32_t d16 = -1;               // /16 words in front of DIR-24-8: -1 per epoch (build_d16), 0 never, 1 always
     int32_t dt_half = -1;           // half-first decision-line reads: -1 per epoch (choose_dt_half), 0, 1
     int32_t dt_parts = 0;           // value parts per (list, class): 0 per epoch (choose_dt_plog2), else 1|2|4|8|16
-    int32_t dt_adapt = 1;           // per-list part counts (<= INFW_DT_PL_LISTS lists): 1 on, 0 off
+    int32_t dt_adapt = 1;           // per-list cut codes (<= INFW_DT_PL_LISTS lists): 1 on, 2 uniform part counts
+                                    // only (no skewed code: A/B runs), 0 off
     int64_t dt_budget_mb = 2048;    // the entry lines of one image stay below this (fewer parts)
     int32_t compile_threads = 0;    // host threads of a full compile: 0 = hardware threads (<= 16)
     int32_t split = -1;             // two-phase classify: -1 when the entry lines exceed split_min_mb, 0 never, 1 always
@@ -321,14 +322,17 @@ void patch_prepare(const HostTables &h, IncState &inc);
 
 // Class-filtered GPU rule records of one 1200-B value (appended to rules) and
 // the per-class first-match decision-table entry lines, INFW_NCLS << plog2 of
-// them (leaf lines appended to leaves).
+// them (leaf lines appended to leaves).  pl_out: the list's cut codes are chosen per class and returned (skew:
+// the skewed codes among them, Options::dt_adapt 1); without it every class is cut into 1 << plog2 parts.
 int compile_rule_list(const uint8_t *val, std::vector<uint64_t> &rules, uint64_t desc_out[INFW_DESC_STRIDE],
-                      infw_dt_line *entry_out, std::vector<infw_dt_line> &leaves, uint32_t plog2, uint32_t *pl_out = nullptr);
+                      infw_dt_line *entry_out, std::vector<infw_dt_line> &leaves, uint32_t plog2,
+                      uint32_t *pl_out = nullptr, bool skew = false);
 // First-match step function of one class list (records {lo16, hi16, result32} in
 // scan order): segment starts ascending from 0 and the result of each segment.
 void step_function(const std::vector<uint64_t> &recs, std::vector<uint32_t> &starts, std::vector<uint32_t> &res);
 // Decision table of one class list (records {lo16, hi16, result32} in scan
-// order): 1 << plog2 entry lines, one per part of the value axis.
+// order): one entry line per part of the value axis as cut code plog2 cuts it (infw_dt_cut_lines; 1 << plog2
+// for the uniform codes 0..4).
 int build_decision_table(const std::vector<uint64_t> &recs, infw_dt_line *entry, std::vector<infw_dt_line> &leaves,
                          uint32_t plog2);
 // Entry (and leaf) lines of a step function: segment starts ascending from 0 and their results.

@@ -279,12 +279,49 @@ INFW_TD uint64_t infw_dt_slot(uint32_t list, int cls, uint32_t v, uint32_t plog2
 // dt_plog2), so a packet's value lands on one of 2^p lines of the region, not 2^dt_plog2: fewer distinct lines
 // per hot (list, class).  The list's word holds p in bits [3 cls, 3 cls + 3).  Lists appended by incremental
 // commits past the table (id >= n_dt_pl) keep the uniform 2^dt_plog2 parts.
+// The field is a cut code.  0..4 are the uniform cuts above.  5..7 exist only in a 16-line region (dt_plog2 == 4)
+// and are skewed cuts (L, a, b): the values below 2^L — where rule sets crowd their service ports — take 2^a lines
+// of their own, line v >> (L - a), and the rest of the value axis takes 2^b wide ones, line 2^a + (v >> (16 - b)),
+// the first of which holds only [2^L, 2^(16 - b)).  A crowded low range then no longer multiplies the lines of the
+// sparse high range: 6, 8 or 12 adjacent lines where the uniform cut needs 16.  All three codes share L = 12 and
+// b = 2 and take a = code - 4, so that the low side's shift, 12 - a, is the uniform cuts' 16 - code.
 #define INFW_DT_PL_LISTS 4096u
+#define INFW_DT_SKEW_L 12u
+#define INFW_DT_SKEW_B 2u
 INFW_TD uint32_t infw_dt_parts_of(uint32_t word, uint32_t list, uint32_t n_dt_pl, int cls, uint32_t plog2) {
     return list < n_dt_pl ? (word >> (3 * cls)) & 7u : plog2;
 }
+// Cut code p as (L, a, b); a uniform cut is the skewed one whose low side is the whole axis (L = 16, no high lines).
+INFW_TD void infw_dt_cut(uint32_t p, uint32_t *L, uint32_t *a, uint32_t *b) {
+    *L = p > 4u ? INFW_DT_SKEW_L : 16u;
+    *a = p > 4u ? p - 4u : p;
+    *b = INFW_DT_SKEW_B;
+}
+INFW_TD uint32_t infw_dt_cut_lines(uint32_t p) {
+    return p > 4u ? (1u << (p - 4u)) + (1u << INFW_DT_SKEW_B) : 1u << p;
+}
+// Values [*lo, *hi) of line q < infw_dt_cut_lines(p) of cut code p (host: the compiler and the models).
+INFW_TD void infw_dt_cut_range(uint32_t p, uint32_t q, uint32_t *lo, uint32_t *hi) {
+    uint32_t L, a, b;
+    infw_dt_cut(p, &L, &a, &b);
+    if (q < (1u << a)) {
+        *lo = q << (L - a);
+        *hi = (q + 1u) << (L - a);
+    } else {
+        q -= 1u << a;
+        *lo = q ? q << (16u - b) : 1u << L;
+        *hi = (q + 1u) << (16u - b);
+    }
+}
+// Line of value v within its region, branch-free: the low side's line, or for a skewed code and a value past 2^L
+// the high side's.
+INFW_TD uint32_t infw_dt_cut_line(uint32_t v, uint32_t p) {
+    const uint32_t top = p > 4u ? 1u << INFW_DT_SKEW_L : 0x10000u;
+    const uint32_t hi = (((1u << (12u - INFW_DT_SKEW_B)) << p) + v) >> (16u - INFW_DT_SKEW_B);  // 2^(p - 4) + (v >> 14)
+    return v < top ? v >> (16u - p) : hi;
+}
 INFW_TD uint64_t infw_dt_slot_p(uint32_t list, int cls, uint32_t v, uint32_t plog2, uint32_t p) {
-    return (((uint64_t)list * INFW_NCLS + (uint32_t)cls) << plog2) | (v >> (16u - p));
+    return (((uint64_t)list * INFW_NCLS + (uint32_t)cls) << plog2) | infw_dt_cut_line(v, p);
 }
 
 // Result word of a compact-leaf code (0 = no match).

@@ -549,11 +549,11 @@ int build_decision_table(const std::vector<uint64_t> &recs, infw_dt_line *entry,
                          uint32_t plog2) {
     std::vector<uint32_t> starts, res;
     step_function(recs, starts, res);
-    const uint32_t span = 65536u >> plog2;
     std::vector<uint32_t> ps, pr;
     size_t j = 0;  // segment holding the part's first value
-    for (uint32_t q = 0; q < (1u << plog2); q++) {
-        const uint32_t lo = q * span, hi = lo + span;
+    for (uint32_t q = 0; q < infw_dt_cut_lines(plog2); q++) {  // plog2: a cut code (infw_tables.h), uniform or skewed
+        uint32_t lo, hi;
+        infw_dt_cut_range(plog2, q, &lo, &hi);
         while (j + 1 < starts.size() && starts[j + 1] <= lo) j++;
         ps.assign(1, lo);
         pr.assign(1, res[j]);
@@ -702,13 +702,13 @@ static uint32_t choose_dt_plog2(const std::vector<const uint8_t *> &vals, const 
     return 4;
 }
 
-// Does every one of the 2^p parts of a step function fit one decision line (no root)?  Mirrors
+// Does every part of a step function cut by code p (infw_tables.h) fit one decision line (no root)?  Mirrors
 // emit_decision_lines' forms: a compact leaf holds 20 segments when all of the part's results have a code.
 static bool parts_fit_one_line(const std::vector<uint32_t> &starts, const std::vector<uint32_t> &res, uint32_t p) {
-    const uint32_t span = 65536u >> p;
     size_t j = 0;
-    for (uint32_t q = 0; q < (1u << p); q++) {
-        const uint32_t lo = q * span, hi = lo + span;
+    for (uint32_t q = 0; q < infw_dt_cut_lines(p); q++) {
+        uint32_t lo, hi;
+        infw_dt_cut_range(p, q, &lo, &hi);
         while (j + 1 < starts.size() && starts[j + 1] <= lo) j++;
         uint32_t S = 1;
         bool compact = infw_dt_result_code(res[j]) <= 0xFFu;
@@ -721,11 +721,13 @@ static bool parts_fit_one_line(const std::vector<uint32_t> &starts, const std::v
     return true;
 }
 
-// pl_out (per-list part counts, infw_tables.h): each class is cut into the fewest 2^p <= 2^plog2 parts that fit
-// one line each, written at the start of its 2^plog2-line region; *pl_out gets p in bits [3c, 3c + 3).
+// pl_out (per-list cut codes, infw_tables.h): each class gets the cut of the fewest lines that fit one line each
+// — a uniform 2^p <= 2^plog2 or, in a 16-line region and with skew, a skewed code; the uniform one on a tie —
+// written at the start of its 2^plog2-line region; *pl_out gets the code in bits [3c, 3c + 3).  The choice reads
+// the rules alone, never the traffic.
 int compile_rule_list(const uint8_t *val, std::vector<uint64_t> &rules,
                       uint64_t desc_out[INFW_DESC_STRIDE], infw_dt_line *entry_out,
-                      std::vector<infw_dt_line> &leaves, uint32_t plog2, uint32_t *pl_out) {
+                      std::vector<infw_dt_line> &leaves, uint32_t plog2, uint32_t *pl_out, bool skew) {
     int rc = 0;
     std::vector<uint64_t> per[INFW_NCLS];
     class_records(val, per);
@@ -735,10 +737,11 @@ int compile_rule_list(const uint8_t *val, std::vector<uint64_t> &rules,
         uint32_t p = plog2;
         if (c < INFW_NCLS && pl_out) {
             step_function(per[c], st, rs);
-            for (uint32_t q = 0; q < plog2; q++)
-                if (parts_fit_one_line(st, rs, q)) {
+            uint32_t lines = 1u << plog2;
+            for (uint32_t q = 0; q < (skew && plog2 == 4 ? 8u : plog2); q++)
+                if (infw_dt_cut_lines(q) < lines && parts_fit_one_line(st, rs, q)) {
                     p = q;
-                    break;
+                    lines = infw_dt_cut_lines(q);
                 }
             pl |= p << (3 * c);
         }
@@ -938,7 +941,7 @@ int compile_tables(const PendingMap &m, HostTables &out, const Options &opt, Inc
             for (size_t lid = a; lid < b && !rc_t[t]; lid++)
                 rc_t[t] = compile_rule_list(m.pool.vals[vid_of_lid[lid]].data(), rules_t[t],
                                             &out.desc[lid * INFW_DESC_STRIDE], &out.dte[lid * ents], leaves_t[t],
-                                            out.dt_plog2, adapt ? &out.dt_pl[lid] : nullptr);
+                                            out.dt_plog2, adapt ? &out.dt_pl[lid] : nullptr, opt.dt_adapt == 1);
         });
         size_t rbase = 0, lbase = 0;
         for (int t = 0; t < nt && !dt_rc; t++) {

@@ -13,6 +13,9 @@
 //   entry32     decision entries of 32 B, a list's classes packed in 128-B lines
 //   quartersQ / partsQxB   entry lines addressed by (list, class, value part)
 //   d16         an 8-B word per (slot, /16) in front of DIR-24-8 answering /16s of <= 3 runs (A | B | A) alone
+//   skew        the skewed cut codes of the decision lines (infw_tables.h infw_dt_cut) over a build without them
+//               (CACHESIM_DT_ADAPT=2; the default build compiles them, so its "current" is this variant);
+//               CACHESIM_SKEW="L,a,b;L,a,b;L,a,b" tries other cuts
 // CACHESIM_CFG / CACHESIM_PREFIXES / CACHESIM_TEMPLATES pick the workload and its table size.
 // Build + run: make cachesim   (tools/cachesim [n_packets])
 #include <stdio.h>
@@ -86,6 +89,8 @@ struct Variant {
                       // of its home set; the lookup reads the home set's line)
     int d16 = 0;      // 1: an 8-B word per (slot, /16) in front of DIR-24-8 answers /16s of <= 3 runs (A | B | A, values
                       // <= 15 bits) by itself; other /16s read their tbl24 word after it
+    int skew = 0;     // 1: adapt plus the skewed cut codes 5..7 of infw_dt_cut (values below 2^L on 2^a lines, the rest
+                      // on 2^b): per (list, class) the code of the fewest lines of <= 20 segments each, uniform on a tie
     int mphf = 0;     // > 0: IPv6 groups in a dense array of mphf-byte records at their rank under a minimal perfect
                       // hash (a random permutation of the groups); an absent group reads one record at a hashed rank
 };
@@ -116,10 +121,45 @@ bool d16_inline(const infw_dev_tables &t, uint32_t slot, uint32_t hi) {
     return nr < 3 || vals[0] == vals[2];
 }
 
+// The skew variant's cuts: CACHESIM_SKEW="L,a,b;L,a,b;L,a,b" replaces the codes 5..7 of infw_dt_cut.
+struct Cut {
+    uint32_t L, a, b;
+};
+Cut g_cut[8];
+uint32_t skew_line(uint32_t code, uint32_t v) {
+    const Cut &c = g_cut[code];
+    return v < (1u << c.L) ? v >> (c.L - c.a) : (1u << c.a) + (v >> (16 - c.b));
+}
+// The compiler's choice (tables.cpp compile_rule_list) over these cuts, from the segment starts alone.
+uint32_t skew_code(const std::vector<uint32_t> &st) {
+    uint32_t best = 4, best_lines = 17;
+    for (uint32_t code = 0; code < 8; code++) {
+        const Cut &c = g_cut[code];
+        const uint32_t lines = code <= 4 ? 1u << code : (1u << c.a) + (1u << c.b);
+        if (lines >= best_lines) continue;
+        uint32_t nseg[16];
+        for (uint32_t q = 0; q < lines; q++) nseg[q] = 1;
+        for (uint32_t x : st)
+            if (x && skew_line(code, x) == skew_line(code, x - 1)) nseg[skew_line(code, x)]++;
+        bool ok = true;
+        for (uint32_t q = 0; q < lines; q++) ok = ok && nseg[q] <= INFW_DT_CLEAF_SEGS;
+        if (ok) best = code, best_lines = lines;
+    }
+    return best;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     const uint64_t n = argc > 1 ? strtoull(argv[1], 0, 10) : (4u << 20);
+    for (uint32_t p = 0; p < 8; p++) {
+        infw_dt_cut(p, &g_cut[p].L, &g_cut[p].a, &g_cut[p].b);
+        if (p > 4 && getenv("CACHESIM_SKEW")) {
+            const char *e = getenv("CACHESIM_SKEW");
+            for (uint32_t k = 5; k < p && e; k++) e = strchr(e, ';') ? strchr(e, ';') + 1 : nullptr;
+            if (e) sscanf(e, "%u,%u,%u", &g_cut[p].L, &g_cut[p].a, &g_cut[p].b);
+        }
+    }
     infw_wl *wl = nullptr;
     const int cfg = getenv("CACHESIM_CFG") ? atoi(getenv("CACHESIM_CFG")) : INFW_WL_CFG2_MIXED_1M;
     const uint32_t npfx = getenv("CACHESIM_PREFIXES") ? (uint32_t)atoi(getenv("CACHESIM_PREFIXES")) : 0;
@@ -158,7 +198,9 @@ int main(int argc, char **argv) {
     }
     for (uint64_t i : order) m.update(&keys[i], reinterpret_cast<const uint8_t *>(&tv[vi[i]]), 0);
     HostTables h;
-    if (compile_tables(m, h, Options())) return 2;
+    Options copt;  // CACHESIM_DT_ADAPT=2: uniform part counts only (the layout before the skewed cut codes)
+    if (getenv("CACHESIM_DT_ADAPT")) copt.dt_adapt = atoi(getenv("CACHESIM_DT_ADAPT"));
+    if (compile_tables(m, h, copt)) return 2;
     const infw_dev_tables t = h.view();
     std::vector<uint32_t> tup(n * 8);
     infw_wl_tuples(wl, 0, n, tup.data(), 8);
@@ -200,12 +242,13 @@ int main(int argc, char **argv) {
                             {"mini4", false, false, 0, 64, 64, 0, 0, 4}, {"mini3", false, false, 0, 64, 64, 0, 0, 3},
                             {"adaptP", false, false, 0, 64, 64, 0, 0, 0, 0, 1},
                             {"clsP", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 1},
+                            {"skew", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 0, 0.8, 0, 0, 1},
                             {"d16", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 0, 0.8, 0, 1},
                             {"set4", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 0, 0.8, 1, 0},
                             {"set4_d16", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 0, 0.8, 1, 1},
                             {"lp2_80", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 2, 0.8},
-                            {"mphf32", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 0, 0.8, 0, 0, 32},
-                            {"mphf64", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 0, 0.8, 0, 0, 64},
+                            {"mphf32", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 0, 0.8, 0, 0, 0, 32},
+                            {"mphf64", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 0, 0.8, 0, 0, 0, 64},
                             {"lp2_60", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 2, 0.6},
                             {"lp4_80", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 4, 0.8},
                             {"lp4_60", false, false, 0, 64, 64, 0, 0, 0, 0, 0, 0, 4, 0.6},
@@ -633,6 +676,15 @@ int main(int argc, char **argv) {
                     }
                     if (pb < 4) tc[nt - 1].addr = 3 * kSpace + (ei * 16 + (val >> (16 - pb))) * 64;
                 }
+                bool skewed = false;
+                if (t.dt_plog2 == 4 && V.skew) {
+                    static std::vector<int8_t> cbest;
+                    if (cbest.empty()) cbest.assign((size_t)h.n_lists * INFW_NCLS, -1);
+                    int8_t &cb = cbest[ei];
+                    if (cb < 0) cb = (int8_t)skew_code(seg_starts[ei]);
+                    skewed = cb > 4;
+                    tc[nt - 1].addr = 3 * kSpace + (ei * 16 + skew_line((uint32_t)cb, val)) * 64;
+                }
                 if (t.dt_plog2 == 4 && V.cls_p && cls_plog[cls] < 4)
                     tc[nt - 1].addr = 3 * kSpace + (ei * 16 + (val >> (16 - cls_plog[cls]))) * 64;
                 if (t.dt_plog2 && V.mini) {  // mini entry first; the 64-B line only for parts with more segments
@@ -645,7 +697,7 @@ int main(int argc, char **argv) {
                     if (nseg > (uint32_t)V.mini) tc[nt++] = {S_ENTRY, line_addr};
                 }
                 const uint32_t *w = t.dte[slot_i].w;
-                if (w[0] & INFW_DT_ROOT) {
+                if ((w[0] & INFW_DT_ROOT) && !skewed) {  // (a skewed code is chosen only when every line is a leaf)
                     const uint64_t li = (w[0] & INFW_DT_INDEX) + infw_keys_below(w, 1, 16, val);
                     tc[nt++] = {S_LEAF, 4 * kSpace + li * 64};
                 }
