@@ -14,7 +14,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-functi
 EXTRA    ?=
 
 LIB_SRCS := $(SRC)/abi.cpp $(SRC)/image.cpp $(SRC)/tables.cpp $(SRC)/incremental.cpp $(SRC)/controlplane.cpp \
-            $(SRC)/hostfeed.cpp $(SRC)/classify.hip $(SRC)/pack.hip $(SRC)/patch.hip $(SRC)/xdpchain.hip
+            $(SRC)/hostfeed.cpp $(SRC)/classify.hip $(SRC)/pack.hip $(SRC)/patch.hip $(SRC)/xdpchain.hip \
+            $(SRC)/evdecode.hip
 LIB_OBJS := $(patsubst $(SRC)/%,$(OBJ)/%.o,$(LIB_SRCS))
 HDRS     := include/infw.h include/infw_host.h $(wildcard $(SRC)/*.h)
 
@@ -29,6 +30,7 @@ $(OBJ)/classify.hip.o: HIPFLAGS += -mllvm -amdgpu-atomic-optimizer-strategy=None
 # (and a table image is accepted only by a library of the same build id, so every source that defines the serialised
 # layout — image.cpp's field order, infw_internal.h's HostTables / IncState, incremental.cpp's state — is in it)
 BUILDID_SRCS := $(SRC)/classify.hip $(SRC)/infw_tables.h $(SRC)/infw_launch.h $(SRC)/infw_pack.h $(SRC)/infw_hostpack.h $(SRC)/tables.cpp $(SRC)/pack.hip $(SRC)/xdpchain.hip include/infw.h \
+                $(SRC)/evdecode.hip $(SRC)/infw_evdecode.h \
                 $(SRC)/image.cpp $(SRC)/infw_internal.h $(SRC)/incremental.cpp
 # The flags part is fixed when the Makefile is read (abi.cpp's, which compiles the id in): a target-specific HIPFLAGS
 # of whichever target first needs the header (classify.hip.o's, abi.cpp.o's, the sanitizer objects') must not change it.
@@ -90,7 +92,8 @@ ASAN_FLAGS := -std=c++17 -g -O1 -fPIC -fsanitize=address,undefined -fno-sanitize
 ASAN_SRCS  := $(SRC)/abi.cpp $(SRC)/image.cpp $(SRC)/tables.cpp $(SRC)/incremental.cpp $(SRC)/controlplane.cpp \
               $(SRC)/hostfeed.cpp
 ASAN_OBJS  := $(patsubst $(SRC)/%,$(ASAN_DIR)/%.o,$(ASAN_SRCS))
-HIP_OBJS   := $(OBJ)/classify.hip.o $(OBJ)/pack.hip.o $(OBJ)/patch.hip.o $(OBJ)/xdpchain.hip.o
+HIP_OBJS   := $(OBJ)/classify.hip.o $(OBJ)/pack.hip.o $(OBJ)/patch.hip.o $(OBJ)/xdpchain.hip.o \
+              $(OBJ)/evdecode.hip.o
 $(ASAN_DIR)/%.o: $(SRC)/% $(HDRS) $(OBJ)/infw_build_id.h
 	@mkdir -p $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -c $< -o $@

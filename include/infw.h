@@ -18,7 +18,7 @@
  *     externally serialised, like ebpfsyncer.go:62,72-73 (e.mu).  The data
  *     path and the readers — infw_classify* (infw_classify_xdp_rings
  *     among them), infw_pack_frames*,
- *     infw_events_capture, infw_stats_read*, infw_table_info,
+ *     infw_events_capture*, infw_events_decode, infw_stats_read*, infw_table_info,
  *     infw_debug_walk, infw_debug_keys_read, infw_classify_variant — may run
  *     on any number of other threads concurrently with them and with each
  *     other; each batch observes exactly one committed table epoch;
@@ -658,6 +658,52 @@ int infw_classify_xdp_rings_ex(infw_ctx *ctx, int dev, const struct infw_xdp_rin
 int infw_events_capture_xdp_rings(infw_ctx *ctx, int dev, const struct infw_xdp_ring *rings, uint32_t n_rings,
                                   const struct infw_event_rec *events, uint64_t events_cap,
                                   const uint64_t *events_count, struct infw_event_sample *samples, void *stream);
+
+/*  - Decoded deny events: what the events reader makes of each perf sample     */
+/*    before it prints (events.go:77-166): the sample's header, the packet cut   */
+/*    to PktLength, and gopacket's eager Ethernet -> IPv4 / IPv6 -> TCP / UDP /  */
+/*    SCTP / ICMP decode of it, for the first layer of each type the syslog      */
+/*    lines carry.  infw/events.py (decode_sample, gopacket_layers) is the       */
+/*    specification, quirks included: IPv4, IPv6, TCP, UDP and SCTP layers exist */
+/*    even when their decode fails (nil addresses / zero ports), ICMP layers     */
+/*    only on success, IPv4 payloads are cut to the total length, fragments stop */
+/*    at the IPv4 layer, IPv6 extension headers are not followed.  A 64-B record */
+/*    per 272-B sample: the host is left with the formatting.                    */
+#define INFW_EVL_IPV4   0x01u   /* a layer of that type exists (Packet.Layer(t) != nil) */
+#define INFW_EVL_IPV6   0x02u
+#define INFW_EVL_TCP    0x04u
+#define INFW_EVL_UDP    0x08u
+#define INFW_EVL_SCTP   0x10u
+#define INFW_EVL_ICMPV4 0x20u
+#define INFW_EVL_ICMPV6 0x40u
+#define INFW_EVL_IP4_ADDRS 0x100u  /* ip4_src/ip4_dst hold addresses (else Go's nil: "<nil>") */
+#define INFW_EVL_IP6_ADDRS 0x200u
+#define INFW_EVL_SHORT  0x40000000u /* body shorter than pktLength: binary.Read fails, no lines */
+#define INFW_EVL_BADHDR 0x80000000u /* size < 8: "Parsing perf event header" */
+struct infw_event_decoded {          /* 64 B, no holes; arrays of it 16-B aligned */
+    struct event_hdr_st hdr;         /*  0 copied from the sample (zeros with BADHDR) */
+    uint32_t layers;                 /*  8 INFW_EVL_* */
+    uint16_t body;                   /* 12 size - 8: bytes behind the header (0 -> "EOF", else "unexpected EOF"); */
+                                     /*    a size above 268 counts as 268, 0 with BADHDR */
+    uint8_t icmp_type, icmp_code;    /* 14 first ICMPv4 / ICMPv6 layer */
+    uint16_t sport, dport;           /* 16 first TCP / UDP / SCTP layer, host order; 0/0 when its decode failed */
+    uint8_t ip4_src[4], ip4_dst[4];  /* 20 first IPv4 layer */
+    uint8_t ip6_src[16], ip6_dst[16];/* 28 first IPv6 layer */
+    uint8_t pad[4];                  /* 60 zero */
+};
+/* decoded[k] for k < min(*events_count, events_cap), from samples[k] alone: no */
+/* other slot of either array is read or written, and a written record is       */
+/* written whole (unused fields and pad zero).  A record with SHORT or BADHDR   */
+/* has no layer bits.  Nothing a sample holds makes the call read outside that  */
+/* sample's 272 bytes.  Stream-ordered after the capture: the count is read on  */
+/* the device, no host synchronisation; asynchronous.  samples, decoded: device */
+/* memory of events_cap slots, 8-byte and 16-byte aligned.  -EINVAL: a NULL     */
+/* samples, events_count or decoded with events_cap != 0, or a misaligned       */
+/* samples / decoded; -ENODEV: a host-only context; events_cap == 0 returns 0   */
+/* and launches nothing.  The host form is infw_events_decode_host              */
+/* (infw_host.h): byte-identical records.                                       */
+int infw_events_decode(infw_ctx *ctx, int dev, const struct infw_event_sample *samples, uint64_t events_cap,
+                       const uint64_t *events_count, struct infw_event_decoded *decoded, void *stream);
 
 /* Host-resident batch: the SoA streams, result words and verdicts live in   */
 /* host memory (as a cgo caller hands them over).  The batch goes through    */

@@ -32,6 +32,13 @@ int infw_xdp_host_events(const uint8_t *umem, const struct infw_xdp_desc *descs,
                          const uint32_t *results, struct infw_event_sample *samples, uint64_t cap,
                          uint64_t *count);
 
+/* infw_events_decode (infw.h) for samples in host memory, such as the ones the */
+/* builders here write: decoded[k] from samples[k] for k < n, byte for byte the */
+/* records the device call writes (one restatement of the parse serves both).   */
+/* No alignment is asked of either array.  Pure host function: no context or    */
+/* device.  0, or -EINVAL for a NULL array with n != 0.                         */
+int infw_events_decode_host(const struct infw_event_sample *samples, uint64_t n, struct infw_event_decoded *decoded);
+
 /* ------------------------------------------------------------------------ */
 /* DPDK-style bursts (SURVEY.md §8f-3 "AF_XDP/DPDK-style NIC feed"): frames  */
 /* anywhere in host memory, one pointer per frame — an rte_mbuf burst's       */

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "../../include/infw_host.h"
+#include "infw_evdecode.h"
 
 #include <sched.h>
 #include <stdio.h>
@@ -505,5 +506,18 @@ extern "C" int infw_xdp_host_events(const uint8_t *umem, const struct infw_xdp_d
         k++;
     }
     *count = k;
+    return 0;
+}
+
+// infw_events_decode on the host: the shared parse (infw_evdecode.h) over each slot where it lies.
+extern "C" int infw_events_decode_host(const struct infw_event_sample *samples, uint64_t n,
+                                       struct infw_event_decoded *decoded) {
+    static_assert(sizeof(infw_event_decoded) == 4 * INFW_EVD_WORDS, "the record is the parse's 16 words");
+    if (n && (!samples || !decoded)) return -EINVAL;
+    for (uint64_t k = 0; k < n; k++) {
+        uint32_t w[INFW_EVD_WORDS];
+        infw_event_decode(infw_evd_mem_reader{reinterpret_cast<const uint8_t *>(samples + k)}, w);
+        memcpy(reinterpret_cast<uint8_t *>(decoded) + k * sizeof(infw_event_decoded), w, sizeof w);
+    }
     return 0;
 }

@@ -106,6 +106,10 @@ int infw_launch_event_samples_xdp_rings(const infw_xdp_ring_ent *ents, uint32_t 
 int infw_launch_event_samples_xdp(const uint8_t *umem, const infw_xdp_desc *descs, uint64_t n,
                                   const infw_event_rec *ev, uint64_t cap, const uint64_t *count,
                                   infw_event_sample *samples, uint32_t cus, hipStream_t stream);
+// infw_events_decode (evdecode.hip): decoded[k] from samples[k] for k < min(*count, cap), one record per lane, the
+// parse of infw_evdecode.h over the wave's slots staged in LDS.  Asynchronous.  0, -EIO.
+int infw_launch_events_decode(const infw_event_sample *samples, uint64_t cap, const uint64_t *count,
+                              infw_event_decoded *decoded, uint32_t cus, hipStream_t stream);
 }
 // The chain pass's tiling: descriptors per workgroup of the reduce / emit kernels, tile summaries per round of the
 // carry kernel (infw/_native.py mirrors them for the tests' ring shapes).

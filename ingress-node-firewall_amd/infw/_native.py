@@ -140,6 +140,19 @@ class XdpRingsEx(C.Structure):
 EVENT_SAMPLE_BYTES = 272  # INFW_EVENT_SAMPLE_BYTES: u32 perf raw size + raw sample (hdr, <= 256 B, pad)
 
 
+class EventDecoded(C.Structure):
+    """struct infw_event_decoded (include/infw.h), 64 B: what the events reader makes of one perf sample."""
+    _fields_ = [("hdr", EventHdrSt), ("layers", C.c_uint32), ("body", C.c_uint16), ("icmp_type", C.c_uint8),
+                ("icmp_code", C.c_uint8), ("sport", C.c_uint16), ("dport", C.c_uint16), ("ip4_src", C.c_uint8 * 4),
+                ("ip4_dst", C.c_uint8 * 4), ("ip6_src", C.c_uint8 * 16), ("ip6_dst", C.c_uint8 * 16),
+                ("pad", C.c_uint8 * 4)]
+
+
+# INFW_EVL_*: the layers of a decoded record
+EVL_IPV4, EVL_IPV6, EVL_TCP, EVL_UDP, EVL_SCTP, EVL_ICMPV4, EVL_ICMPV6 = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
+EVL_IP4_ADDRS, EVL_IP6_ADDRS, EVL_SHORT, EVL_BADHDR = 0x100, 0x200, 0x40000000, 0x80000000
+
+
 class TableInfo(C.Structure):
     _fields_ = [("epoch", C.c_uint64), ("n_entries", C.c_uint64), ("n_if_slots", C.c_uint32),
                 ("n_lists", C.c_uint32), ("n_rules", C.c_uint64), ("n_tbl8_groups", C.c_uint64),
@@ -175,7 +188,7 @@ ABI_SYMBOLS = [
     "infw_events_capture_xdp", "infw_classify_xdp_host", "infw_classify_xdp_rings",
     "infw_classify_xdp_rings_ex", "infw_events_capture_xdp_rings", "infw_classify_xdp_rings_split",
     "infw_pack_xdp_host", "infw_launch_counts", "infw_xdp_host_events", "infw_classify_bursts_host",
-    "infw_pack_burst_host", "infw_burst_host_events",
+    "infw_pack_burst_host", "infw_burst_host_events", "infw_events_decode", "infw_events_decode_host",
 ]
 ABI_VERSION = 4  # include/infw.h INFW_ABI_VERSION
 INPUT_SOA, INPUT_COMPACT, INPUT_FRAMES, INPUT_XDP = 0, 1, 2, 3  # INFW_INPUT_*
@@ -282,6 +295,8 @@ _sig = {
     "infw_classify_xdp_rings_ex": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), C.c_uint32, P(XdpRingsEx), C.c_void_p]),
     "infw_events_capture_xdp_rings": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), C.c_uint32, C.c_void_p, C.c_uint64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infw_events_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infw_events_decode_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "infw_classify_xdp_rings_split": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), P(XdpRingSplit), C.c_uint32,
                                                 C.c_void_p, C.c_void_p]),
 }
@@ -351,7 +366,7 @@ for _name, (_res, _args) in _wsig.items():
     _f.argtypes = _args
 
 assert C.sizeof(EventHdrSt) == 8 and C.sizeof(EventRec) == 24 and C.sizeof(XdpRing) == 48
-assert C.sizeof(XdpRingSplit) == 16
+assert C.sizeof(XdpRingSplit) == 16 and C.sizeof(EventDecoded) == 64
 if lib.infw_abi_version() != ABI_VERSION:
     raise ImportError(f"{LIB_PATH}: ABI {lib.infw_abi_version()}, these bindings are ABI {ABI_VERSION}: rebuild (make)")
 

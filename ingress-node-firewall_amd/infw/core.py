@@ -492,6 +492,23 @@ class Classifier:
         check(N.lib.infw_events_capture(self._ctx, dev, C.byref(fb), n_frames, events.data_ptr(), cap,
                                         events_count.data_ptr(), samples.data_ptr(), sp), "events_capture")
 
+    def events_decode(self, samples, count, cap: int, out=None, dev: int = 0, stream=None):
+        """infw_events_decode: the perf samples an events_capture* call wrote (`samples`: uint8 device tensor of at
+        least cap x 272 B, `count`: the int64 [1] events_count tensor, read on the device) -> a (cap, 64) uint8 device
+        tensor of infw_event_decoded records, rows below min(count, cap) written.  infw.events.format_records turns
+        them into the reader's lines.  `out`: write into this tensor (at least cap x 64 B) and return it."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(samples.device)
+        sp = stream if isinstance(stream, int) else stream.cuda_stream
+        assert samples.numel() >= cap * N.EVENT_SAMPLE_BYTES, "samples: one 272-B slot per event record"
+        if out is None:
+            out = torch.empty((cap, C.sizeof(N.EventDecoded)), dtype=torch.uint8, device=samples.device)
+        assert out.numel() >= cap * C.sizeof(N.EventDecoded), "out: one 64-B record per slot"
+        check(N.lib.infw_events_decode(self._ctx, dev, samples.data_ptr(), cap, count.data_ptr(), out.data_ptr(), sp),
+              "events_decode")
+        return out
+
     def set_launch(self, block: int = 768, scan_group: int = 0, blocks_per_cu: int = 2) -> None:
         """Launch shape of the classify kernel (tuning knob; see include/infw.h)."""
         check(N.lib.infw_set_launch(self._ctx, block, scan_group, blocks_per_cu), "set_launch")
@@ -658,6 +675,18 @@ def xdp_host_events(umem: np.ndarray, descs: np.ndarray, ifindex: int, results: 
                                      r.ctypes.data if n else None, out.ctypes.data if cap else None, cap, C.byref(k)),
           "xdp_host_events")
     return out[:cap], k.value
+
+
+def events_decode_host(samples: np.ndarray) -> np.ndarray:
+    """infw_events_decode_host (include/infw_host.h): perf samples in host memory (n x 272 uint8, as the host event
+    builders or a copy of the device's return them) -> n x 64 uint8 infw_event_decoded records, byte for byte what
+    Classifier.events_decode writes."""
+    s = np.ascontiguousarray(samples, np.uint8).reshape(-1, N.EVENT_SAMPLE_BYTES)
+    n = s.shape[0]
+    out = np.zeros((n, C.sizeof(N.EventDecoded)), np.uint8)
+    check(N.lib.infw_events_decode_host(s.ctypes.data if n else None, n, out.ctypes.data if n else None),
+          "events_decode_host")
+    return out
 
 
 def pack_xdp_host(umem: np.ndarray, descs: np.ndarray, ifindex: int) -> Dict[str, np.ndarray]:

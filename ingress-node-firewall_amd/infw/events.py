@@ -7,6 +7,8 @@ the raw sample = event_hdr_st + min(len, 256) frame bytes + alignment pad, kerne
   read_samples      perf.Reader.Read() -> Record.RawSample             events.go:64-75
   decode_sample     header / packet parse, iface lookup, syslog lines   events.go:77-166
   gopacket_layers   gopacket.NewPacket(packet, LayerTypeEthernet, gopacket.Default) for the layers the consumer logs
+  format_records    the same lines from the 64-B records infw_events_decode / infw_events_decode_host make of the
+                    samples (csrc/infw_evdecode.h restates decode_sample + gopacket_layers, which stay the specification)
 
 gopacket v1.1.19 (the reference's go.mod pin; vendored at vendor/github.com/google/gopacket) is a third-party
 dependency; gopacket_layers restates the decoders the consumer depends on — layers/ethernet.go decodeEthernet,
@@ -194,4 +196,50 @@ def drain(samples: np.ndarray, count: int, if_name: Callable[[int], Optional[str
         a, b = decode_sample(raw, if_name)
         sys_lines += a
         log += b
+    return sys_lines, log
+
+
+# struct infw_event_decoded (include/infw.h): one 64-B record per perf sample, as infw_events_decode /
+# infw_events_decode_host write it
+DECODED = np.dtype([("ifId", "<u2"), ("ruleId", "<u2"), ("action", "u1"), ("hdr_pad", "u1"), ("pktLength", "<u2"),
+                    ("layers", "<u4"), ("body", "<u2"), ("icmp_type", "u1"), ("icmp_code", "u1"), ("sport", "<u2"),
+                    ("dport", "<u2"), ("ip4_src", "u1", 4), ("ip4_dst", "u1", 4), ("ip6_src", "u1", 16),
+                    ("ip6_dst", "u1", 16), ("pad", "u1", 4)])
+assert DECODED.itemsize == 64
+EVL_IPV4, EVL_IPV6, EVL_TCP, EVL_UDP, EVL_SCTP, EVL_ICMPV4, EVL_ICMPV6 = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
+EVL_IP4_ADDRS, EVL_IP6_ADDRS, EVL_SHORT, EVL_BADHDR = 0x100, 0x200, 0x40000000, 0x80000000
+
+
+def format_records(decoded: np.ndarray, count: int, if_name: Callable[[int], Optional[str]]) -> Tuple[List[str], List[str]]:
+    """drain() for decoded records: `decoded` holds one 64-B record per slot of the ring (cap x 64 uint8, or any
+    array of cap * 64 bytes), `count` is the capture's event count.  The same (syslog lines, daemon log lines) as
+    drain(samples, count, if_name) over the samples the records were decoded from — only formatting is left."""
+    recs = np.ascontiguousarray(decoded).view(np.uint8).reshape(-1).view(DECODED)
+    k = min(int(count), recs.shape[0])
+    sys_lines: List[str] = []
+    log: List[str] = [f"Perf event ring buffer full, dropped {int(count) - k} samples"] if int(count) > k else []
+    for r in recs[:k]:
+        ly = int(r["layers"])
+        if ly & EVL_BADHDR:
+            log.append("Parsing perf event header err: unexpected EOF")
+            continue
+        if ly & EVL_SHORT:
+            log.append("Parsing perf event packet header : " + ("EOF" if r["body"] == 0 else "unexpected EOF"))
+            continue
+        name = if_name(int(r["ifId"]))
+        if name is None:
+            log.append(f"lookup network iface {r['ifId']}: route ip+net: no such network interface")
+            continue
+        sys_lines.append(f"ruleId {r['ruleId']} action {convert_xdp_action_to_string(int(r['action']))} "
+                         f"len {r['pktLength']} if {name}\n")
+        for bit, addrs, fam in ((EVL_IPV4, EVL_IP4_ADDRS, "ip4"), (EVL_IPV6, EVL_IP6_ADDRS, "ip6")):
+            if ly & bit:
+                src, dst = (bytes(r[fam + "_src"]), bytes(r[fam + "_dst"])) if ly & addrs else (None, None)
+                sys_lines.append(f"\tipv{fam[2]} src addr {go_ip_string(src)} dst addr {go_ip_string(dst)}\n")
+        for bit, l4 in ((EVL_TCP, "tcp"), (EVL_UDP, "udp"), (EVL_SCTP, "sctp")):
+            if ly & bit:
+                sys_lines.append(f"\t{l4} srcPort {r['sport']} dstPort {r['dport']}\n")
+        for bit, ic in ((EVL_ICMPV4, "icmpv4"), (EVL_ICMPV6, "icmpv6")):
+            if ly & bit:
+                sys_lines.append(f"\t{ic} type {r['icmp_type']} code {r['icmp_code']}\n")
     return sys_lines, log

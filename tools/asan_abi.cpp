@@ -3,7 +3,8 @@
 // rejected inputs), map edits single and batched with their flag semantics, lookups, the get_next_key walk, full and
 // incremental commits, the debug walk of the committed host image, and table images — export, import, re-export,
 // incremental edits on exporter and importer alike, and corrupt images: every header byte and bytes spread over the
-// whole payload flipped, truncations, trailing bytes, import into a busy context and into one emptied by deletes.
+// whole payload flipped, truncations, trailing bytes, import into a busy context and into one emptied by deletes; and
+// the deny-event decode (infw_events_decode_host) over garbage samples, each in a heap block of exactly its size.
 //   asan_abi                 the self-test above; prints "ok"
 //   asan_abi import FILE     import FILE into a fresh host-only context; prints "rc=<errno> <last error>"
 //                            (tests/test_image_cpu.py feeds it structurally corrupted images with a valid hash)
@@ -15,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "infw.h"
+#include "infw_host.h"
 
 #define CHECK(cond)                                                                                        \
     do {                                                                                                   \
@@ -315,6 +316,25 @@ static int selftest() {
         CHECK(infw_classify_variant(o.c, 0, INFW_INPUT_SOA, 0, name, 4) == -ERANGE);
         CHECK(infw_classify_variant(o.c, 0, 7, 0, name, sizeof name) == -EINVAL);
     }
+    // infw_events_decode_host over garbage: each sample alone in a heap block of exactly its 272 bytes, so a read
+    // outside the slot is a report; sizes and packet lengths around every bound, IPv4 / IPv6 chains of random headers
+    for (int it = 0; it < 20000; it++) {
+        std::vector<uint8_t> s(INFW_EVENT_SAMPLE_BYTES), d(sizeof(infw_event_decoded), 0xAB);
+        for (auto &b : s) b = (uint8_t)rnd();
+        const uint32_t sizes[] = {0, 7, 8, 22, 60, 268, 269, 0xFFFFFFFFu}, size = sizes[rnd() % 8];
+        const uint16_t lens[] = {0, 13, 14, 15, 34, 54, 256, 260, 261}, len = lens[rnd() % 9];
+        memcpy(s.data(), &size, 4);
+        if (rnd() & 1) memcpy(s.data() + 10, &len, 2);
+        s[24] = rnd() & 1 ? 0x08 : 0x86, s[25] = s[24] == 0x08 ? 0x00 : 0xDD;
+        for (uint32_t at = 26; at + 40 <= INFW_EVENT_SAMPLE_BYTES; at += rnd() & 1 ? 20 : 40) {
+            s[at] = 0x45 + rnd() % 3, s[at + 2] = s[at + 3] = 0, s[at + 9] = rnd() & 1 ? 4 : 41;  // IPv4 view
+            s[at + 6] = rnd() & 1 ? 4 : 41;                                                          // IPv6 view
+        }
+        CHECK(infw_events_decode_host(reinterpret_cast<const infw_event_sample *>(s.data()), 1,
+                                      reinterpret_cast<infw_event_decoded *>(d.data())) == 0);
+        CHECK(d[60] == 0 && d[63] == 0);
+    }
+    CHECK(infw_events_decode_host(nullptr, 1, nullptr) == -EINVAL && infw_events_decode_host(nullptr, 0, nullptr) == 0);
     printf("asan_abi: %zu keys, images %zu / %zu bytes, %zu corrupt images refused\nok\n", keys.size(), img.size(),
            small_img.size(), refused);
     return 0;

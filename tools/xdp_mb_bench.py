@@ -18,7 +18,10 @@ device), and infw_classify_xdp_rings followed by what a host does without it —
 one numpy boolean index per ring and list on one thread (a C loop would be faster than this host form); its issue time
 is the whole step.  The lists of the two are compared once.
 
+--decode [N]: infw_events_decode alone over N (default 2^20) sample slots — see decode_mode.
+
     python tools/xdp_mb_bench.py [--n 16777216] [--rounds 20] [--events] [--rings [64] --ring-n 2048 [--split]]
+    python tools/xdp_mb_bench.py --decode [1048576] [--rounds 20]
 """
 import ctypes as C
 import argparse
@@ -149,6 +152,52 @@ def rings_mode(args, clf, wl):
                                       for k, v in d.items()}}))
 
 
+def decode_mode(args):
+    """infw_events_decode over --decode records of the case-table mix of tests/test_events_decode.py, HIP events around
+    each call; beside it the path it replaces (D2H of the 272-B slots, then events.drain on the host) and the new
+    host side (D2H of the 64-B records, then events.format_records), the two Python loops over the first 65536 records."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_events_decode import NAMES, TABLE
+    from infw import events as E
+    n, dev, sub = args.decode, torch.device("cuda", 0), 1 << 16
+    clf = infw.Classifier(devices=[0])
+    smp = torch.from_numpy(np.resize(TABLE, (n, TABLE.shape[1]))).to(dev)
+    cnt = torch.tensor([n], dtype=torch.int64, device=dev)
+    out = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    smp_h, out_h = torch.empty(smp.shape, dtype=torch.uint8).pin_memory(), torch.empty(out.shape, dtype=torch.uint8).pin_memory()
+    arms = {"decode": lambda: clf.events_decode(smp, cnt, n, out=out),
+            "d2h_samples": lambda: smp_h.copy_(smp, non_blocking=True),
+            "d2h_records": lambda: out_h.copy_(out, non_blocking=True)}
+    ms = {k: [] for k in arms}
+    for rnd in range(-3, args.rounds):  # three warm-up rounds
+        for k, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rnd >= 0:
+                ms[k].append(e0.elapsed_time(e1))
+    assert np.array_equal(out_h.numpy()[:sub], infw.events_decode_host(smp_h.numpy()[:sub])), "device != host records"
+    t0 = time.perf_counter()
+    want = E.drain(smp_h.numpy()[:sub], sub, NAMES)
+    t1 = time.perf_counter()
+    got = E.format_records(out_h.numpy()[:sub], sub, NAMES)
+    t2 = time.perf_counter()
+    assert got == want, "format_records != drain"
+    rates = W.line_rates(0)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    ns = med["decode"] * 1e6 / n
+    print(json.dumps({"records": n, "rounds": args.rounds, "build_id": infw.build_id(), "event_ms_median": med,
+                      "event_ms_min": {k: min(v) for k, v in ms.items()}, "event_ms_max": {k: max(v) for k, v in ms.items()},
+                      "decode_ns_per_record": ns, "stream_GB_per_s": rates["stream_GB_per_s"],
+                      "decode_fraction_of_stream": (272 + 64) / ns / rates["stream_GB_per_s"],
+                      "d2h_samples_ns_per_record": med["d2h_samples"] * 1e6 / n,
+                      "d2h_records_ns_per_record": med["d2h_records"] * 1e6 / n,
+                      "host_drain_ns_per_record": (t1 - t0) * 1e9 / sub,
+                      "host_format_records_ns_per_record": (t2 - t1) * 1e9 / sub}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 24)
@@ -157,8 +206,11 @@ def main():
     ap.add_argument("--rings", type=int, nargs="?", const=64, default=0)
     ap.add_argument("--ring-n", type=int, default=2048)
     ap.add_argument("--split", action="store_true")
+    ap.add_argument("--decode", type=int, nargs="?", const=1 << 20, default=0)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
+    if args.decode:
+        return decode_mode(args)
     n, dev = args.n, torch.device("cuda", 0)
     wl = W.Workload(W.CFG2_MIXED_1M)
     clf = infw.Classifier(devices=[0], max_entries=wl.n_entries + 16)
