@@ -15,7 +15,7 @@ EXTRA    ?=
 
 LIB_SRCS := $(SRC)/abi.cpp $(SRC)/image.cpp $(SRC)/tables.cpp $(SRC)/incremental.cpp $(SRC)/controlplane.cpp \
             $(SRC)/hostfeed.cpp $(SRC)/classify.hip $(SRC)/pack.hip $(SRC)/patch.hip $(SRC)/xdpchain.hip \
-            $(SRC)/evdecode.hip
+            $(SRC)/evdecode.hip $(SRC)/evsort.hip
 LIB_OBJS := $(patsubst $(SRC)/%,$(OBJ)/%.o,$(LIB_SRCS))
 HDRS     := include/infw.h include/infw_host.h $(wildcard $(SRC)/*.h)
 
@@ -30,7 +30,7 @@ $(OBJ)/classify.hip.o: HIPFLAGS += -mllvm -amdgpu-atomic-optimizer-strategy=None
 # (and a table image is accepted only by a library of the same build id, so every source that defines the serialised
 # layout — image.cpp's field order, infw_internal.h's HostTables / IncState, incremental.cpp's state — is in it)
 BUILDID_SRCS := $(SRC)/classify.hip $(SRC)/infw_tables.h $(SRC)/infw_launch.h $(SRC)/infw_pack.h $(SRC)/infw_hostpack.h $(SRC)/tables.cpp $(SRC)/pack.hip $(SRC)/xdpchain.hip include/infw.h \
-                $(SRC)/evdecode.hip $(SRC)/infw_evdecode.h \
+                $(SRC)/evdecode.hip $(SRC)/infw_evdecode.h $(SRC)/evsort.hip \
                 $(SRC)/image.cpp $(SRC)/infw_internal.h $(SRC)/incremental.cpp
 # The flags part is fixed when the Makefile is read (abi.cpp's, which compiles the id in): a target-specific HIPFLAGS
 # of whichever target first needs the header (classify.hip.o's, abi.cpp.o's, the sanitizer objects') must not change it.
@@ -93,7 +93,7 @@ ASAN_SRCS  := $(SRC)/abi.cpp $(SRC)/image.cpp $(SRC)/tables.cpp $(SRC)/increment
               $(SRC)/hostfeed.cpp
 ASAN_OBJS  := $(patsubst $(SRC)/%,$(ASAN_DIR)/%.o,$(ASAN_SRCS))
 HIP_OBJS   := $(OBJ)/classify.hip.o $(OBJ)/pack.hip.o $(OBJ)/patch.hip.o $(OBJ)/xdpchain.hip.o \
-              $(OBJ)/evdecode.hip.o
+              $(OBJ)/evdecode.hip.o $(OBJ)/evsort.hip.o
 $(ASAN_DIR)/%.o: $(SRC)/% $(HDRS) $(OBJ)/infw_build_id.h
 	@mkdir -p $(ASAN_DIR)
 	g++ $(ASAN_FLAGS) -c $< -o $@

@@ -18,7 +18,8 @@
  *     externally serialised, like ebpfsyncer.go:62,72-73 (e.mu).  The data
  *     path and the readers — infw_classify* (infw_classify_xdp_rings
  *     among them), infw_pack_frames*,
- *     infw_events_capture*, infw_events_decode, infw_stats_read*, infw_table_info,
+ *     infw_events_sort, infw_events_capture*, infw_events_decode,
+ *     infw_stats_read*, infw_table_info,
  *     infw_debug_walk, infw_debug_keys_read, infw_classify_variant — may run
  *     on any number of other threads concurrently with them and with each
  *     other; each batch observes exactly one committed table epoch;
@@ -630,7 +631,10 @@ int infw_events_capture_xdp(infw_ctx *ctx, int dev, const uint8_t *umem, const s
 /* them, the chain bounded by its OWN ring: it ends at the first descriptor    */
 /* with PKT_CONTD clear or at the ring's last descriptor; no descriptor of     */
 /* another ring is read, and no byte outside [buffer_j, buffer_j + len_j) of a */
-/* chain member.                                                               */
+/* chain member.  A caller who wants the samples in packet order                */
+/* (infw_events_sort) uses the stand-alone capture after the sort, not the     */
+/* fused `samples`: the fused samples lie in the order the records were        */
+/* appended.                                                                   */
 /* Errnos as infw_classify_xdp_rings, plus -EINVAL for size <                  */
 /* sizeof(struct infw_xdp_rings_ex), flags != 0, events without events_count,  */
 /* samples without events, samples not 8-byte aligned.  -ENOMEM: the scratch   */
@@ -704,6 +708,41 @@ struct infw_event_decoded {          /* 64 B, no holes; arrays of it 16-B aligne
 /* (infw_host.h): byte-identical records.                                       */
 int infw_events_decode(infw_ctx *ctx, int dev, const struct infw_event_sample *samples, uint64_t events_cap,
                        const uint64_t *events_count, struct infw_event_decoded *decoded, void *stream);
+
+/*  - Deny events in packet order: the records of a buffer sorted on the device,  */
+/*    between the classify that appended them and the capture that reads them.   */
+/*    One AF_XDP ring is one NIC queue and one CPU, whose perf records reach the */
+/*    reader in arrival order (kernel.c:392-399, events.go:77-96); the classify  */
+/*    kernels append in no order across waves (above).                           */
+/* Ordering: let m = min(*events_count, events_cap), read on the device.         */
+/* Afterwards events[0 .. m) holds the same m records, ordered by                */
+/* key = min(pkt_index, index_bound) ascending; each record is written whole     */
+/* (24 B, `reserved` included).                                                  */
+/* Stability: records with equal keys keep their relative order, so the records  */
+/* of several calls that share a buffer stay grouped as appended, and records of */
+/* another batch (pkt_index >= index_bound) end up last, in their original       */
+/* order.                                                                        */
+/* index_bound: the caller's exclusive bound on pkt_index — the batch's n, or    */
+/* the rings' flat total.  It lets the host choose the number of 8-bit digit     */
+/* passes (ceil(bits(index_bound) / 8)) without reading anything back;           */
+/* index_bound == 0 means the full 64-bit key (8 passes).                        */
+/* Untouched memory: events[m .. events_cap) and *events_count are neither read  */
+/* nor written.  If records were lost (*events_count > events_cap) the set that  */
+/* was kept stays whatever the classify kept; the sort only orders it.           */
+/* Stream order: after the classify, before the capture — infw_events_capture*   */
+/* and infw_events_decode work slot by slot from events[k], so samples and       */
+/* decoded records then come out in packet order.  Asynchronous: the count is    */
+/* read on the device, no host synchronisation, no wait for work already queued. */
+/* -EINVAL: a NULL events or events_count with events_cap != 0, events not       */
+/* 8-byte aligned, events_cap >= 2^32.  -ENODEV: a host-only context.  -ENOMEM:  */
+/* no per-call scratch from the context's pool — 40 B per slot of events_cap     */
+/* (the record's copy and two 8-B {key, slot} pairs; 48 B when index_bound is 0  */
+/* or above 2^32 - 1), 1 KiB per 2048 slots and 1 KiB, each array rounded up to  */
+/* 16 B; nothing of it outlives the call.  -EIO: a launch error.  events_cap ==  */
+/* 0 returns 0 and launches nothing.  Nothing is launched when an error is       */
+/* returned.                                                                     */
+int infw_events_sort(infw_ctx *ctx, int dev, struct infw_event_rec *events, uint64_t events_cap,
+                     const uint64_t *events_count, uint64_t index_bound, void *stream);
 
 /* Host-resident batch: the SoA streams, result words and verdicts live in   */
 /* host memory (as a cgo caller hands them over).  The batch goes through    */

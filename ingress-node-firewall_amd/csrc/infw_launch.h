@@ -110,7 +110,14 @@ int infw_launch_event_samples_xdp(const uint8_t *umem, const infw_xdp_desc *desc
 // parse of infw_evdecode.h over the wave's slots staged in LDS.  Asynchronous.  0, -EIO.
 int infw_launch_events_decode(const infw_event_sample *samples, uint64_t cap, const uint64_t *count,
                               infw_event_decoded *decoded, uint32_t cus, hipStream_t stream);
+// infw_events_sort (evsort.hip): events[0 .. min(*count, cap)) stably by min(pkt_index, bound) (bound 0: the whole
+// key), an LSD radix sort over (key, slot) pairs in scratch from `pool` — 40 B per slot, 48 B when bound is 0 or above
+// 2^32 - 1, and 1 KiB per tile of INFW_EVSORT_TILE slots — with ceil(bits(bound) / 8) passes of three launches each.
+// cap < 2^32.  Asynchronous.  0, -EIO on a launch error, -ENOMEM when there is no pool or the scratch cannot be had.
+int infw_launch_events_sort(infw_event_rec *events, uint64_t cap, const uint64_t *count, uint64_t bound,
+                            hipMemPool_t pool, hipStream_t stream);
 }
+#define INFW_EVSORT_TILE 2048
 // The chain pass's tiling: descriptors per workgroup of the reduce / emit kernels, tile summaries per round of the
 // carry kernel (infw/_native.py mirrors them for the tests' ring shapes).
 #define INFW_XDP_CHAIN_TILE 256

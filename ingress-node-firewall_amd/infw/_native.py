@@ -189,6 +189,7 @@ ABI_SYMBOLS = [
     "infw_classify_xdp_rings_ex", "infw_events_capture_xdp_rings", "infw_classify_xdp_rings_split",
     "infw_pack_xdp_host", "infw_launch_counts", "infw_xdp_host_events", "infw_classify_bursts_host",
     "infw_pack_burst_host", "infw_burst_host_events", "infw_events_decode", "infw_events_decode_host",
+    "infw_events_sort",
 ]
 ABI_VERSION = 4  # include/infw.h INFW_ABI_VERSION
 INPUT_SOA, INPUT_COMPACT, INPUT_FRAMES, INPUT_XDP = 0, 1, 2, 3  # INFW_INPUT_*
@@ -297,6 +298,7 @@ _sig = {
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "infw_events_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infw_events_decode_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "infw_events_sort": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "infw_classify_xdp_rings_split": (C.c_int, [C.c_void_p, C.c_int, P(XdpRing), P(XdpRingSplit), C.c_uint32,
                                                 C.c_void_p, C.c_void_p]),
 }

@@ -509,6 +509,20 @@ class Classifier:
               "events_decode")
         return out
 
+    def events_sort(self, events, count, cap: int, index_bound: int, dev: int = 0, stream=None) -> None:
+        """infw_events_sort: the first min(count, cap) deny-event records of `events` (uint8 device tensor of at least
+        cap x 24 B; `count`: the int64 [1] events_count tensor, read on the device) into packet order, in place: stably
+        by min(pkt_index, index_bound).  `index_bound`: the batch's n or the rings' flat total (0: the whole 64-bit
+        key).  Run it after the classify and before events_capture* / events_decode, which then write their slots in
+        packet order."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(events.device)
+        sp = stream if isinstance(stream, int) else stream.cuda_stream
+        assert events.numel() >= cap * C.sizeof(N.EventRec), "events: one 24-B record per slot"
+        check(N.lib.infw_events_sort(self._ctx, dev, events.data_ptr(), cap, count.data_ptr(), index_bound, sp),
+              "events_sort")
+
     def set_launch(self, block: int = 768, scan_group: int = 0, blocks_per_cu: int = 2) -> None:
         """Launch shape of the classify kernel (tuning knob; see include/infw.h)."""
         check(N.lib.infw_set_launch(self._ctx, block, scan_group, blocks_per_cu), "set_launch")

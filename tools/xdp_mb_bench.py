@@ -19,9 +19,11 @@ one numpy boolean index per ring and list on one thread (a C loop would be faste
 is the whole step.  The lists of the two are compared once.
 
 --decode [N]: infw_events_decode alone over N (default 2^20) sample slots — see decode_mode.
+--sort [N]: infw_events_sort alone over N (default 2^20) event records, beside torch's stable argsort — see sort_mode.
 
     python tools/xdp_mb_bench.py [--n 16777216] [--rounds 20] [--events] [--rings [64] --ring-n 2048 [--split]]
     python tools/xdp_mb_bench.py --decode [1048576] [--rounds 20]
+    python tools/xdp_mb_bench.py --sort [1048576] [--rounds 20]
 """
 import ctypes as C
 import argparse
@@ -198,6 +200,41 @@ def decode_mode(args):
                       "host_format_records_ns_per_record": (t2 - t1) * 1e9 / sub}))
 
 
+def sort_mode(args):
+    """infw_events_sort over --sort records with random pkt_index below index_bound = 2^27 (4 digit passes), HIP events
+    around each call, alternated with the yardstick a caller has without it: torch.argsort(key, stable=True) and an
+    index_select of the records viewed as (n, 3) int64 — which also needs the count on the host, not timed here.  The
+    sort is in place, so the unsorted records are copied back before each timed call, outside the events."""
+    n, dev, bound = args.sort, torch.device("cuda", 0), 1 << 27
+    clf = infw.Classifier(devices=[0])
+    src = torch.randint(0, 1 << 62, (n, 3), dtype=torch.int64, device=dev, generator=torch.Generator(dev).manual_seed(5))
+    src[:, 2] = src[:, 2] % bound
+    ev, out = torch.empty_like(src), torch.empty_like(src)
+    cnt = torch.tensor([n], dtype=torch.int64, device=dev)
+    arms = {"events_sort": lambda: clf.events_sort(ev.view(torch.uint8).reshape(-1), cnt, n, bound),
+            "torch_argsort_select": lambda: torch.index_select(ev, 0, torch.argsort(ev[:, 2], stable=True), out=out)}
+    ms = {k: [] for k in arms}
+    for rnd in range(-3, args.rounds):  # three warm-up rounds
+        for k, fn in arms.items():
+            ev.copy_(src)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rnd >= 0:
+                ms[k].append(e0.elapsed_time(e1))
+    ev.copy_(src)
+    arms["events_sort"]()
+    assert torch.equal(ev, out), "events_sort != stable argsort + index_select"
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    print(json.dumps({"records": n, "index_bound": bound, "rounds": args.rounds, "build_id": infw.build_id(),
+                      "event_ms_median": med, "event_ms_min": {k: min(v) for k, v in ms.items()},
+                      "event_ms_max": {k: max(v) for k, v in ms.items()},
+                      "sort_ns_per_record": med["events_sort"] * 1e6 / n,
+                      "torch_over_events_sort": med["torch_argsort_select"] / med["events_sort"]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 24)
@@ -207,10 +244,13 @@ def main():
     ap.add_argument("--ring-n", type=int, default=2048)
     ap.add_argument("--split", action="store_true")
     ap.add_argument("--decode", type=int, nargs="?", const=1 << 20, default=0)
+    ap.add_argument("--sort", type=int, nargs="?", const=1 << 20, default=0)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     if args.decode:
         return decode_mode(args)
+    if args.sort:
+        return sort_mode(args)
     n, dev = args.n, torch.device("cuda", 0)
     wl = W.Workload(W.CFG2_MIXED_1M)
     clf = infw.Classifier(devices=[0], max_entries=wl.n_entries + 16)
